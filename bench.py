@@ -10,11 +10,17 @@ draws + both Adam updates) on one synthetic batch that is resident in HBM before
 Workload = BASELINE.json configs[2] ("paper config: 4 in -> 18 out, 256x256, latent=768"), the configuration the
 metric "radar frames/sec (G+D step) 4->18 @256^2" is quoted on; per-GPU batch fixed (weak scaling).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, `ms_per_step`, config, memory).  `--full` adds
+everything else the bench measures, after the timed steps: the live HIP-event roofline step, the other arithmetic modes and the
+fast-semantics leg (`also`), the CPU baseline, and the full record in a side file (`--detail`).
+`--dump-outputs DIR` writes what the last timed step computed - its losses and the model state it updated - as DIR/<name>.npy.
 """
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -48,8 +54,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=int(os.environ.get("DGMR_BENCH_BATCH", "16")), help="per-GPU batch")
     ap.add_argument("--workload", default="paper", choices=["paper", "cfg2", "cfg5", "smoke"])
     ap.add_argument("--fast", action="store_true", help="strict_reference_semantics=False (skip discarded work)")
-    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "off", "only"])
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline, the `also` legs and the CPU baseline and write the detail "
+                         "file (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the losses and the model state of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "off", "only"],
+                    help="with --full: sample = time the CPU baseline; only = the CPU baseline alone, no GPU (needs no --full)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline step")
     ap.add_argument("--tune", default="", help="A/B switch for kernel development: variant,ksplit,window,wgrad_window for "
                                                "dgmr_conv_tune (-1 = the library's own choice, the default)")
     ap.add_argument("--precision", default=os.environ.get("DGMR_PRECISION", "mixed"), choices=["f32", "bf16x6", "mixed", "bf16x3", "bf16"],
@@ -57,11 +69,12 @@ def parse():
                          "fp32-faithful products on the bf16 pipe | mixed (default) = bf16x3 (16-bit products) with the discriminator "
                          "forward in bf16x6 | bf16x3 | bf16")
     ap.add_argument("--also", default="auto", choices=["auto", "on", "off"],
-                    help="also time the same build in the other arithmetic modes and report them in an `also` block: exact f32 (the "
-                         "reference's arithmetic: >= 10 steps after 3 warm-ups, with its own roofline block), bf16x6 and plain bf16 "
-                         "(a few steps each); auto = on for single-GPU runs")
+                    help="with --full: also time the same build in the other arithmetic modes and report them in an `also` block: exact "
+                         "f32 (the reference's arithmetic: >= 10 steps after 3 warm-ups, with its own roofline block), bf16x6 and plain "
+                         "bf16 (a few steps each); auto = on for single-GPU runs")
     ap.add_argument("--also-f32-steps", type=int, default=10)
-    ap.add_argument("--detail", default="", help="side file for the full record (default gpurun_out/bench_detail.json, relative to the repo)")
+    ap.add_argument("--detail", default="", help="with --full: side file for the full record (default bench_out/bench_detail.json, "
+                                                 "relative to the repo)")
     ap.add_argument("--force-dist", action="store_true",
                     help="with --gpus 1: still create the RCCL process group (world 1), attach the gradient exchange with "
                          "force_exchange so that every bucket goes through ncclAllReduce and the buffers through ncclBroadcast")
@@ -69,7 +82,8 @@ def parse():
 
 
 def respawn_under_torchrun(args):
-    """`python bench.py --gpus N` without a launcher: re-exec as N ranks (one per GPU, RCCL) under torch.distributed.run."""
+    """`python bench.py --gpus N` without a launcher: run N ranks (one per GPU, RCCL) under torch.distributed.run in a child process
+    and exit with its status."""
     import socket
 
     with socket.socket() as sk:
@@ -77,7 +91,7 @@ def respawn_under_torchrun(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 WORKLOADS = {
@@ -301,7 +315,8 @@ def compact_line(full, detail_path=None, limit=LINE_LIMIT):
 
 
 def time_steps(model, batch, first_idx, n, barrier):
-    """n training steps bracketed by barrier + device synchronisation; returns (seconds, per-step device ms from HIP events)."""
+    """n training steps bracketed by barrier + device synchronisation; returns (seconds, per-step device ms from HIP events).
+    time_steps.last: what the last step returned."""
     import torch
 
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
@@ -314,7 +329,7 @@ def time_steps(model, batch, first_idx, n, barrier):
         if step_sync:
             torch.cuda.synchronize()
         h0 = time.perf_counter()
-        model.training_step(batch, first_idx + i)
+        time_steps.last = model.training_step(batch, first_idx + i)
         evs[i + 1].record()
         ms_ = torch.cuda.memory_stats()
         host.append((round(1e3 * (time.perf_counter() - h0), 1), round(torch.cuda.memory_reserved() / 2**30, 2),
@@ -323,6 +338,37 @@ def time_steps(model, batch, first_idx, n, barrier):
     dt = time.perf_counter() - t0
     time_steps.host = host  # per step: host ms inside training_step, reserved GB, device allocations so far, allocator retries
     return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(n)]
+
+
+DUMP_SAMPLE = 4096  # elements kept per state tensor (a fixed, seeded sample of larger ones)
+DUMP_LIMIT = 64 << 20  # bytes in all
+
+
+def dump_outputs(out_dir, losses, model):
+    """What the timed path hands its caller after its last step, as out_dir/<name>.npy: `loss.<name>` - the losses training_step
+    returns (float64) - and `state.<key>` - every parameter and buffer of the model it updated in place (Adam steps, u / v, BatchNorm
+    statistics; float32, integer buffers float64).  A tensor of more than DUMP_SAMPLE elements is reduced to DUMP_SAMPLE of them at
+    sorted indices drawn from a generator seeded with the key, so that the same arguments dump the same positions in every run and
+    build."""
+    import zlib
+
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"loss.{k}": np.asarray([float(v)], dtype=np.float64) for k, v in losses.items()}
+    for k, v in model.state_dict().items():
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        flat = flat.cpu()
+        arrays[f"state.{k}"] = (flat.float() if flat.is_floating_point() else flat.double()).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), total
 
 
 def main():
@@ -338,9 +384,14 @@ def main():
 
     import __graft_entry__ as ge
 
-    ge.build()
+    # an up-to-date build is only loaded: build() takes a lock file beside the library, which a tree built by someone else (or
+    # read-only) does not allow - and the benchmark needs nothing written
+    if ge._needs_rebuild():
+        ge.build()
     import skillful_nowcasting_amd as S
     from skillful_nowcasting_amd import _lib
+
+    _lib.load()  # dlopen + check that every symbol of include/dgmr_hip.h is exported
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -396,6 +447,8 @@ def main():
         model.training_step(batch, i)
     dt, step_ms = time_steps(model, batch, args.warmup, args.steps, barrier)
     step_host = list(time_steps.host)
+    if args.dump_outputs and rank == 0:  # before anything else runs a step on the model
+        dump_outputs(args.dump_outputs, time_steps.last, model)
     # data parallel: every rank must hold bit-identical parameters after the timed steps (same all-reduced gradients, same Adam)
     replicas_in_sync = None
     if use_dist:
@@ -547,14 +600,14 @@ def main():
         return roof
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roofline = measure_roofline(args.precision, ms_per_step, args.warmup + args.steps)
 
     # The same build in the other arithmetic modes, witnessed by the same run.  The exact-f32 leg is the reference's own arithmetic
     # (train/run.py:232 precision=32): a first-class line of >= 10 steps after 3 warm-ups with its own per-kernel roofline block
     # (peak 157.3 TF).  bf16x6 (fp32-faithful products on the bf16 pipe) and plain bf16 (BASELINE.json configs[1]'s dtype) ride along.
     also = None
-    if (args.also == "on" or (args.also == "auto" and world == 1)) and not args.fast:
+    if args.full and (args.also == "on" or (args.also == "auto" and world == 1)) and not args.fast:
         also = {}
         legs = {"f32": (3, max(1, args.also_f32_steps)), "bf16x6": (2, 5), "bf16": (2, 5)}
         for mode, (w_m, n) in legs.items():
@@ -616,18 +669,21 @@ def main():
             out["roofline"] = roofline
         if also:
             out["also"] = also
-        if args.cpu_baseline != "off" and world == 1:  # (the contract: on rank 0 at N = 1 only - the other ranks would sit in the final barrier)
+        if args.full and args.cpu_baseline != "off" and world == 1:  # (the contract: on rank 0 at N = 1 only - the other ranks would sit in the final barrier)
             out["cpu_baseline"] = cpu_baseline_reference(kw, hw, T) or cpu_baseline(kw, hw, T)
             if args.workload in REFERENCE_MEASURED:
                 out["cpu_baseline"]["reference_measured"] = REFERENCE_MEASURED[args.workload]
-        # the full record (per_kernel_detail, per-step times, the PMC launch records) goes to a side file; stdout gets ONE bounded line
-        detail_path = args.detail or os.path.join("gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(os.path.join(ROOT, detail_path)) or ".", exist_ok=True)
-            with open(os.path.join(ROOT, detail_path), "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as e:  # (a read-only tree must not cost the bench line)
-            detail_path = f"not written: {e}"
+        # --full: the full record (per_kernel_detail, per-step times, the PMC launch records) goes to a side file; stdout gets ONE
+        # bounded line
+        detail_path = None
+        if args.full:
+            detail_path = args.detail or os.path.join("bench_out", "bench_detail.json")
+            try:
+                os.makedirs(os.path.dirname(os.path.join(ROOT, detail_path)) or ".", exist_ok=True)
+                with open(os.path.join(ROOT, detail_path), "w") as f:
+                    json.dump(out, f, indent=1)
+            except OSError as e:  # (a read-only tree must not cost the bench line)
+                detail_path = f"not written: {e}"
         final_line = compact_line(out, detail_path)
     if use_dist:
         dist.barrier()

@@ -14,11 +14,12 @@ import os
 import sys
 
 import torch
-from safetensors.torch import save_file
+from safetensors.torch import save_file as _save_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import _stubs  # noqa: E402
+from oracle.make_ref import SRC as REFERENCE_ROOT  # noqa: E402
 
 _stubs.install()
 torch.autograd.set_detect_anomaly(False)
@@ -37,6 +38,23 @@ from dgmr.layers import AttentionLayer, ConvGRU  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 os.makedirs(OUT, exist_ok=True)
+PART_BYTES = 1000 * 1024  # a fixture file above this size is committed as consecutive byte ranges <name>.safetensors.partNNN
+
+
+def save_file(rec, path, metadata=None):
+    """safetensors.torch.save_file, then split into parts of at most PART_BYTES when larger (tests/conftest.py:load_golden joins them)."""
+    import glob
+
+    for old in glob.glob(path) + glob.glob(path + ".part*"):
+        os.remove(old)
+    _save_file(rec, path, metadata=metadata)
+    if os.path.getsize(path) <= PART_BYTES:
+        return
+    data = open(path, "rb").read()
+    os.remove(path)
+    for i in range(0, len(data), PART_BYTES):
+        with open(f"{path}.part{i // PART_BYTES:03d}", "wb") as f:
+            f.write(data[i:i + PART_BYTES])
 
 
 def _is_buffer_key(k):
@@ -160,6 +178,8 @@ def main():
     training_step_golden()
     training_steps_adv_golden()
     validation_step_golden()
+    model_api_golden()
+    extract_frames_golden()
 
 
 TS_KW = dict(forecast_steps=2, input_channels=1, output_shape=128, latent_channels=384, context_channels=192, generation_steps=2)
@@ -378,6 +398,68 @@ def validation_step_golden():
     rec["images"], rec["future"] = images, future
     save_file(rec, os.path.join(OUT, "validation_step.safetensors"),
               metadata={"keys": json.dumps(keys), "kw": json.dumps(TS_KW), "seeds": "[42, 43, 45]"})
+
+
+MODEL_API_KW = dict(forecast_steps=2, input_channels=1, output_shape=128, latent_channels=384, context_channels=192, generation_steps=2)
+
+
+def model_api_golden():
+    """What tests/test_model_api.py needs to check interchange with the reference without it: the unmodified reference's DGMR at
+    MODEL_API_KW, seeded 11 - its state_dict keys in order with shapes and dtypes, per-tensor (sum, abs-sum, first, last) fingerprints,
+    its constructor's parameter names - and what its `save_pretrained` writes: the file names, config.json verbatim and the
+    model.safetensors header (tensor names, dtypes, shapes, byte offsets, metadata) without the tensor bytes.  -> model_api_reference.json"""
+    import inspect
+    import struct
+    import tempfile
+
+    from dgmr import DGMR
+
+    torch.manual_seed(11)
+    model = DGMR(**MODEL_API_KW)
+    torch.autograd.set_detect_anomaly(False)  # (the reference's constructor turns it on)
+    sd = model.state_dict()
+    keys = [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()]
+    fp = []
+    for v in sd.values():
+        t = v.detach().double().flatten()
+        fp.append([t.sum().item(), t.abs().sum().item(), t[0].item(), t[-1].item()])
+    with tempfile.TemporaryDirectory() as d:
+        model.save_pretrained(d)
+        files = sorted(os.listdir(d))
+        config_text = open(os.path.join(d, "config.json")).read()
+        with open(os.path.join(d, "model.safetensors"), "rb") as f:
+            n = struct.unpack("<Q", f.read(8))[0]
+            header = json.loads(f.read(n))
+    params = [p for p in inspect.signature(DGMR.__init__).parameters if p != "self"]
+    rec = {"kw": MODEL_API_KW, "seed": 11, "state_dict": keys, "fingerprints": fp, "init_parameters": params,
+           "save_pretrained": {"files": files, "config.json": config_text, "model.safetensors header": header}}
+    with open(os.path.join(OUT, "model_api_reference.json"), "w") as f:
+        json.dump(rec, f, separators=(",", ":"))
+    print("model_api_reference:", len(keys), "state tensors,", len(header) - 1, "in model.safetensors, files", files)
+
+
+def extract_frames_golden():
+    """The reference's train/run.py data split (`extract_input_and_target_frames`, NUM_INPUT_FRAMES / NUM_TARGET_FRAMES) on seeded
+    frames.  run.py itself cannot be imported here (wandb / datasets / Lightning): its constants and that function are executed from
+    its source text.  -> extract_frames.safetensors"""
+    import ast
+
+    import numpy as np
+
+    src = open(os.path.join(REFERENCE_ROOT, "train", "run.py")).read()
+    tree = ast.parse(src)
+    keep = [n for n in tree.body if (isinstance(n, ast.Assign) and any(getattr(t, "id", "").startswith("NUM_") for t in n.targets))
+            or (isinstance(n, ast.FunctionDef) and n.name == "extract_input_and_target_frames")]
+    ns = {}
+    exec(compile(ast.Module(body=keep, type_ignores=[]), "run.py", "exec"), ns)
+    frames = np.random.default_rng(0).random((30, 5, 7, 2)).astype(np.float32)
+    rx, ry = ns["extract_input_and_target_frames"](frames)
+    rec = {"frames": torch.from_numpy(frames), "input_frames": torch.from_numpy(np.ascontiguousarray(rx)),
+           "target_frames": torch.from_numpy(np.ascontiguousarray(ry))}
+    save_file(rec, os.path.join(OUT, "extract_frames.safetensors"),
+              metadata={"NUM_INPUT_FRAMES": str(ns["NUM_INPUT_FRAMES"]), "NUM_TARGET_FRAMES": str(ns["NUM_TARGET_FRAMES"]),
+                        "frames": "np.random.default_rng(0).random((30, 5, 7, 2)).astype(np.float32)"})
+    print("extract_frames:", rx.shape, ry.shape, ns["NUM_INPUT_FRAMES"], ns["NUM_TARGET_FRAMES"])
 
 
 if __name__ == "__main__":

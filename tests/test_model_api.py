@@ -2,12 +2,14 @@
 
   * Hugging Face `save_pretrained` / `from_pretrained` round trips of DGMR and its four publishable parts - the five tests of the
     reference's tests/test_model.py:341-399, through the `dgmr` import alias (skillful_nowcasting_amd.install_as);
-  * interchange WITH the reference (build container only, where /root/reference exists): a state dict / safetensors directory /
-    Lightning-style .ckpt written by the unmodified reference loads into this package and vice versa, key for key, bit for bit;
+  * interchange WITH the reference: a state dict / safetensors directory / Lightning-style .ckpt written by the unmodified reference
+    loads into this package and vice versa, key for key, bit for bit - against what the reference writes and reads, recorded in
+    tests/golden/model_api_reference.json (oracle/gen_golden.py);
   * the data path (train/run.py:118-158) and the visualisation grids (dgmr/dgmr.py:302-327).
 """
+import json
 import os
-import sys
+import struct
 
 import numpy as np
 import pytest
@@ -15,9 +17,7 @@ import torch
 from torch.testing import assert_close
 
 import skillful_nowcasting_amd as S
-
-REF = "/root/reference"
-needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "dgmr")), reason="needs /root/reference (build container)")
+from conftest import GOLDEN, assert_init_fingerprints, load_golden
 
 
 @pytest.fixture(scope="module")
@@ -95,57 +95,108 @@ def test_lightning_checkpoint_round_trip(tmp_path):
             S.DGMR.load_from_checkpoint(tmp_path / "bad.ckpt")
 
 
-def _reference():
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from oracle import _stubs
-
-    _stubs.install()
-    for name in [k for k in sys.modules if k == "dgmr" or k.startswith("dgmr.")]:  # drop the alias: import the REAL reference
-        del sys.modules[name]
-    import dgmr as ref
-
-    torch.autograd.set_detect_anomaly(False)
-    return ref
+def _reference_record():
+    """The unmodified reference's DGMR at `kw`, seeded `seed`: state_dict layout and per-tensor fingerprints, constructor parameters,
+    and what its save_pretrained writes (file names, config.json, the model.safetensors header without the tensor bytes)."""
+    with open(os.path.join(GOLDEN, "model_api_reference.json")) as f:
+        return json.load(f)
 
 
-@needs_reference
+def _layout(sd):
+    return [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()]
+
+
+def _fingerprints(sd):
+    """Per tensor (sum, abs-sum, first, last) in float64, as oracle/gen_golden.py records them."""
+    rows = []
+    for v in sd.values():
+        t = v.detach().double().flatten()
+        rows.append([t.sum().item(), t.abs().sum().item(), t[0].item(), t[-1].item()])
+    return torch.tensor(rows, dtype=torch.float64)
+
+
+_ST_DTYPES = {"F32": torch.float32, "I64": torch.int64}
+
+
+def _safetensors_header(path):
+    with open(path, "rb") as f:
+        return json.loads(f.read(struct.unpack("<Q", f.read(8))[0]))
+
+
+def _write_as_reference(rec, sd, path):
+    """The directory the reference's save_pretrained writes for these tensors: its config.json verbatim and a model.safetensors with
+    its header - tensor names, dtypes, shapes, byte offsets, shared-tensor metadata - around the bytes of `sd`."""
+    save = rec["save_pretrained"]
+    os.makedirs(path)
+    with open(os.path.join(path, "config.json"), "w") as f:
+        f.write(save["config.json"])
+    header = save["model.safetensors header"]
+    entries = {k: e for k, e in header.items() if k != "__metadata__"}
+    blob = bytearray(max(e["data_offsets"][1] for e in entries.values()))
+    for k, e in entries.items():
+        t = sd[k].detach().contiguous()
+        assert list(t.shape) == e["shape"] and t.dtype == _ST_DTYPES[e["dtype"]], k
+        lo, hi = e["data_offsets"]
+        blob[lo:hi] = t.numpy().tobytes()
+    head = json.dumps(header, separators=(",", ":")).encode()
+    head += b" " * (-len(head) % 8)
+    with open(os.path.join(path, "model.safetensors"), "wb") as f:
+        f.write(struct.pack("<Q", len(head)) + head + bytes(blob))
+
+
 def test_interchange_with_the_reference(tmp_path):
     """Reference -> here and here -> reference: state_dict, save_pretrained directory, .ckpt."""
-    kw = dict(forecast_steps=2, input_channels=1, output_shape=128, latent_channels=384, context_channels=192, generation_steps=2)
-    try:
-        ref = _reference()
-        torch.manual_seed(11)
-        theirs = ref.DGMR(**kw)
-        torch.manual_seed(12)
-        ours = S.DGMR(**kw)
-        assert list(ours.state_dict().keys()) == list(theirs.state_dict().keys())
-        # 1. reference state dict -> our model (strict), tensors equal afterwards, conv weights re-laid out channels-last
-        ours.load_state_dict(theirs.state_dict(), strict=True)
-        for (k, a), b in zip(ours.state_dict().items(), theirs.state_dict().values()):
+    from safetensors.torch import load_file
+
+    rec = _reference_record()
+    kw = rec["kw"]
+    # the reference's seeded state dict: its construction is reproduced here and pinned to the recorded layout and fingerprints,
+    # its tensors laid out as the reference holds them (plain contiguous)
+    torch.manual_seed(rec["seed"])
+    theirs = {k: v.detach().clone().contiguous() for k, v in S.DGMR(**kw).state_dict().items()}
+    assert _layout(theirs) == rec["state_dict"]
+    assert_init_fingerprints(_fingerprints(theirs), torch.tensor(rec["fingerprints"], dtype=torch.float64), list(theirs))
+    torch.manual_seed(12)
+    ours = S.DGMR(**kw)
+    assert _layout(ours.state_dict()) == rec["state_dict"]
+    # 1. reference state dict -> our model (strict), tensors equal afterwards, conv weights re-laid out channels-last
+    ours.load_state_dict(theirs, strict=True)
+    for (k, a), b in zip(ours.state_dict().items(), theirs.values()):
+        assert torch.equal(a, b), k
+    assert ours.discriminator.temporal_discriminator.d1.first_conv_3x3.weight_orig.is_contiguous(memory_format=torch.channels_last_3d)
+    # 2. a directory written by the reference's save_pretrained -> our from_pretrained
+    _write_as_reference(rec, theirs, tmp_path / "theirs")
+    loaded = S.DGMR.from_pretrained(tmp_path / "theirs")
+    for (k, a), b in zip(loaded.state_dict().items(), theirs.values()):
+        assert torch.equal(a, b), k
+    assert loaded.generation_steps == 2 and loaded.latent_channels == 384
+    # 3. our save_pretrained -> what the reference's from_pretrained reads: the config.json entries named like its constructor's
+    #    parameters, and model.safetensors with the names, dtypes, shapes and shared-tensor metadata of the file it writes itself
+    torch.manual_seed(13)
+    mine = S.DGMR(**kw)
+    mine.save_pretrained(tmp_path / "mine")
+    save = rec["save_pretrained"]
+    assert sorted(os.listdir(tmp_path / "mine")) == save["files"]
+    with open(tmp_path / "mine" / "config.json") as f:
+        config = json.load(f)
+    assert {k: v for k, v in config.items() if k in rec["init_parameters"]} == json.loads(save["config.json"])
+    header, ref_header = _safetensors_header(tmp_path / "mine" / "model.safetensors"), save["model.safetensors header"]
+    assert header.get("__metadata__") == ref_header.get("__metadata__")
+    shapes = lambda h: {k: (e["dtype"], e["shape"]) for k, e in h.items() if k != "__metadata__"}  # noqa: E731
+    assert shapes(header) == shapes(ref_header)
+    back = load_file(tmp_path / "mine" / "model.safetensors")
+    mine_sd = mine.state_dict()
+    for k, b in back.items():
+        assert torch.equal(b, mine_sd[k]), k
+    for alias, k in ref_header["__metadata__"].items():  # tensors the file holds once, under the name the metadata maps them to
+        assert torch.equal(back[k], mine_sd[alias]), alias
+    assert set(back) | set(ref_header["__metadata__"]) == set(mine_sd)
+    # 4. a reference-side Lightning checkpoint -> our loader
+    torch.save({"state_dict": theirs, "hyper_parameters": kw}, tmp_path / "theirs.ckpt")
+    if not S.dgmr.HAVE_LIGHTNING:
+        from_ckpt = S.DGMR.load_from_checkpoint(tmp_path / "theirs.ckpt")
+        for (k, a), b in zip(from_ckpt.state_dict().items(), theirs.values()):
             assert torch.equal(a, b), k
-        assert ours.discriminator.temporal_discriminator.d1.first_conv_3x3.weight_orig.is_contiguous(memory_format=torch.channels_last_3d)
-        # 2. a directory written by the reference's save_pretrained -> our from_pretrained
-        theirs.save_pretrained(tmp_path / "theirs")
-        loaded = S.DGMR.from_pretrained(tmp_path / "theirs")
-        for (k, a), b in zip(loaded.state_dict().items(), theirs.state_dict().values()):
-            assert torch.equal(a, b), k
-        assert loaded.generation_steps == 2 and loaded.latent_channels == 384
-        # 3. our save_pretrained -> the reference's from_pretrained
-        torch.manual_seed(13)
-        mine = S.DGMR(**kw)
-        mine.save_pretrained(tmp_path / "mine")
-        back = ref.DGMR.from_pretrained(tmp_path / "mine")
-        for (k, a), b in zip(back.state_dict().items(), mine.state_dict().values()):
-            assert torch.equal(a, b), k
-        # 4. a reference-side Lightning checkpoint -> our loader
-        torch.save({"state_dict": theirs.state_dict(), "hyper_parameters": kw}, tmp_path / "theirs.ckpt")
-        if not S.dgmr.HAVE_LIGHTNING:
-            from_ckpt = S.DGMR.load_from_checkpoint(tmp_path / "theirs.ckpt")
-            for (k, a), b in zip(from_ckpt.state_dict().items(), theirs.state_dict().values()):
-                assert torch.equal(a, b), k
-    finally:
-        for name in [k for k in sys.modules if k == "dgmr" or k.startswith("dgmr.")]:
-            del sys.modules[name]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -163,25 +214,18 @@ def test_extract_input_and_target_frames():
     assert np.array_equal(xs[:, 0], x[..., 0])
 
 
-@needs_reference
 def test_extract_matches_the_reference_function():
-    """The reference's train/run.py cannot be imported here (wandb / datasets / Lightning), so its two data functions are executed
-    from their source text."""
-    import ast
-
+    """The reference's train/run.py data split, recorded on seeded frames (tests/golden/extract_frames, oracle/gen_golden.py: run.py
+    cannot be imported - wandb / datasets / Lightning - so its constants and that function were executed from its source text)."""
     from skillful_nowcasting_amd import data
 
-    src = open(os.path.join(REF, "train", "run.py")).read()
-    tree = ast.parse(src)
-    keep = [n for n in tree.body if (isinstance(n, ast.Assign) and any(getattr(t, "id", "").startswith("NUM_") for t in n.targets))
-            or (isinstance(n, ast.FunctionDef) and n.name == "extract_input_and_target_frames")]
-    ns = {}
-    exec(compile(ast.Module(body=keep, type_ignores=[]), "run.py", "exec"), ns)
+    rec, meta = load_golden("extract_frames")
     frames = np.random.default_rng(0).random((30, 5, 7, 2)).astype(np.float32)
-    rx, ry = ns["extract_input_and_target_frames"](frames)
+    assert np.array_equal(rec["frames"].numpy(), frames)
+    rx, ry = rec["input_frames"].numpy(), rec["target_frames"].numpy()
     x, y = data.extract_input_and_target_frames(frames)
     assert np.array_equal(rx, x) and np.array_equal(ry, y)
-    assert (ns["NUM_INPUT_FRAMES"], ns["NUM_TARGET_FRAMES"]) == (data.NUM_INPUT_FRAMES, data.NUM_TARGET_FRAMES)
+    assert (int(meta["NUM_INPUT_FRAMES"]), int(meta["NUM_TARGET_FRAMES"])) == (data.NUM_INPUT_FRAMES, data.NUM_TARGET_FRAMES)
     assert np.array_equal(np.moveaxis(rx, [0, 1, 2, 3], [0, 2, 3, 1]), data.to_model_layout(x))
 
 

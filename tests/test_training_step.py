@@ -22,7 +22,7 @@ import os
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
+from conftest import GOLDEN, assert_init_fingerprints, load_golden
 
 LR_MAX = 2e-4
 
@@ -122,7 +122,7 @@ def test_seeded_init_matches_reference():
     model = S.DGMR(**kw)
     sd = model.state_dict()
     assert sorted(sd.keys()) == keys
-    assert torch.equal(_checksums(sd, keys), rec["cs0"]), "seeded construction differs from the reference's"
+    assert_init_fingerprints(_checksums(sd, keys), rec["cs0"], keys)
 
 
 def test_oracle_training_step_matches_reference():

@@ -3,7 +3,7 @@
 #   bash tools/gpu_call.sh <tag> [steps...]      steps, in the order given:
 #     tests:<pytest -k expression or file list>   selected -m gpu tests           -> pytest_<n>.log
 #     alltests                                    the whole -m gpu suite          -> pytest_all.log
-#     bench:[VAR=v ...] <bench.py args>           one bench line + detail file (leading VAR=v words: environment)    -> bench_<n>.json / bench_<n>_detail.json
+#     bench:[VAR=v ...] <bench.py args>           one bench.py --full line + detail file (leading VAR=v words: environment) -> bench_<n>.json / bench_<n>_detail.json
 #     prof:<bench.py args>                        rocprofv3 --kernel-trace --stats of a 1-step run (summaries only are kept)
 #     pmc                                         tools/r5_pmc.sh (counters for every conv class)
 #     convbench:<conv_bench.py args>              kernel micro-benchmarks         -> convbench_<n>.log
@@ -32,7 +32,7 @@ for STEP in "$@"; do
     bench)
       ENVV=""  # leading VAR=value words of the argument go to the environment (A/B switches)
       while [[ "${ARG%% *}" == *=* && "${ARG%% *}" != --* ]]; do ENVV="$ENVV ${ARG%% *}"; ARG="${ARG#* }"; done
-      timeout 900 env $ENVV python bench.py $ARG --detail "gpurun_out/$TAG/bench_${n}_detail.json" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; echo "[$n] bench rc=$?"
+      timeout 900 env $ENVV python bench.py $ARG --full --detail "${OUT#"$ROOT"/}/bench_${n}_detail.json" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; echo "[$n] bench rc=$?"
       tail -c 3500 "$OUT/bench_$n.json"; echo; tail -3 "$OUT/bench_$n.err" ;;
     prof)
       ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof$n" -o trace -- \

@@ -1,4 +1,4 @@
-"""bench_detail.json (the full record bench.py writes beside its one-line summary) -> a markdown table of the per-kernel rows.
+"""bench_detail.json (the full record `bench.py --full` writes beside its one-line summary) -> a markdown table of the per-kernel rows.
     python tools/roofline_report.py profiles/r05_final_B16_bench_detail.json > profiles/r05_final_roofline_table.md"""
 import json
 import sys
