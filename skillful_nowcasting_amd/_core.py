@@ -6,14 +6,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-import weakref
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import torch
-from torch.autograd import Function
 
-from ._lib import DETERMINISTIC_DEFAULT, ConvArgs, WgradArgs, call
+from ._lib import DETERMINISTIC_DEFAULT, call, load
 
 _WEIGHTS_EPOCH = 0  # bumped by the optimiser after every in-place parameter update (flip cache key)
 
@@ -21,10 +19,6 @@ _WEIGHTS_EPOCH = 0  # bumped by the optimiser after every in-place parameter upd
 def bump_weights_epoch():
     global _WEIGHTS_EPOCH
     _WEIGHTS_EPOCH += 1
-
-
-def weights_epoch() -> int:
-    return _WEIGHTS_EPOCH
 
 
 # Round 6: an optimiser step marks ITS parameters, not every weight of the process.  The caches of derived weight images (bf16 planes,
@@ -87,8 +81,6 @@ def sums_buffer(groups: int, rows: int, c: int, device, row_blocks: bool = True,
     n = groups * 2 * c
     if not (_DETERMINISTIC and row_blocks):
         return torch.zeros(n, device=device, dtype=torch.float64) if zero else torch.empty(n, device=device, dtype=torch.float64)
-    from ._lib import load
-
     buf = torch.empty(int(load().dgmr_reduce_doubles(groups, rows, c)), device=device, dtype=torch.float64)
     if zero:
         buf[:n].zero_()
@@ -108,8 +100,6 @@ def dot_buffer(groups: int, device) -> torch.Tensor:
     """<P_q, W> accumulators of dgmr_wgrad_reduce: `groups` floats, zeroed (+ the workgroups' rows in deterministic mode)."""
     if not _DETERMINISTIC:
         return torch.zeros(groups, device=device, dtype=torch.float32)
-    from ._lib import load
-
     buf = torch.empty(int(load().dgmr_wgrad_dot_floats(groups)), device=device, dtype=torch.float32)
     buf[:groups].zero_()
     return buf

@@ -2,17 +2,11 @@
 linear), the losses, device-side scalar bookkeeping and the Adam update - autograd Functions over the C ABI."""
 from __future__ import annotations
 
-import ctypes
-import weakref
-from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
-
 import torch
 from torch.autograd import Function
 
-from ._lib import ConvArgs, WgradArgs, call
-from ._core import (BNState, SNCall, _copy, _dims, _p, _stream, bn_prepare, dot_buffer, empty_cl, grad_buffer, require_hip, sums_buffer, colsum_tmp,
-                    to_cl)
+from ._lib import call, load
+from ._core import BNState, SNCall, _p, _stream, bn_prepare, dot_buffer, grad_buffer, require_hip, sums_buffer, colsum_tmp, to_cl
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -221,8 +215,6 @@ class GridCellFn(Function):
         n = targets.numel()
         mult = float(targets.size(3) * targets.size(4)) / float(targets.size(1))
         loss = torch.empty((), device=preds.device, dtype=torch.float32)
-        from ._lib import load
-
         acc = torch.zeros(int(load().dgmr_grid_cell_acc_doubles(n)), device=preds.device, dtype=torch.float64)
         dweight = torch.empty_like(targets)
         call("dgmr_grid_cell_loss", _p(preds), k, n, _p(targets), _p(weights), float(cap), _p(acc), _p(loss), mult, _p(dweight), n,

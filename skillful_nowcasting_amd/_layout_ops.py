@@ -3,16 +3,13 @@ channel concatenation, batch <-> list and time <-> channel moves for the time-ba
 beyond the 2x2 / 2x2x2 averages."""
 from __future__ import annotations
 
-import ctypes
-import weakref
-from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import Sequence
 
 import torch
 from torch.autograd import Function
 
-from ._lib import ConvArgs, WgradArgs, call
-from ._core import _copy, _dims, _p, _stream, colsum_tmp, empty_cl, require_hip, sums_buffer, to_cl
+from ._lib import call
+from ._core import _copy, _dims, _p, _stream, colsum_tmp, empty_cl, require_hip, to_cl
 
 
 # ---------------------------------------------------------------------------------------------------

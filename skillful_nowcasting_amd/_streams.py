@@ -1,23 +1,18 @@
-"""Second-stream scheduling of the backward pass: weight gradients beside the data-gradient chain, an optional branch stream for
-the temporal discriminator, and the joins that order the main stream behind them (no host synchronisation anywhere)."""
+"""Second-stream scheduling of the backward pass: weight gradients beside the data-gradient chain, and the joins that order the main
+stream behind them (no host synchronisation anywhere)."""
 from __future__ import annotations
 
-import ctypes
-import weakref
-from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+import os
+from typing import List
 
 import torch
-from torch.autograd import Function
-
-from ._lib import ConvArgs, WgradArgs, call
 
 # Weight gradients off the critical path: the backward chain only needs each conv's DATA gradient; its weight gradient (window /
 # im2col kernel, slab reduce, spectral-norm finalize - latency-bound kernels at 20-30 % matrix-pipe occupancy) runs on a second
 # stream beside the data-gradient convs of the layers below.  The main stream joins it when the backward pass ends
 # (autograd engine callback), i.e. before anything can read a .grad.
-_SIDE_STREAMS = {}
-_SIDE_PENDING = {}
+_SIDE_STREAMS = {}  # device index -> the device's ONE weight-gradient stream
+_SIDE_PENDING = {}  # device index -> the main stream that has to wait for it
 _SIDE_KEEP = []  # (event after the side work, tensors it reads)
 
 
@@ -36,89 +31,33 @@ class defer_side_join:
         _DEFER_JOIN[0] -= 1
 
 
-_BRANCH_STREAMS = {}
-# opt-in: measured 1044.7 vs 1049.6 ms/step (-0.5 %) with all parity tests green; off by default - autograd warns about the
-# AccumulateGrad stream of inputs shared by the two branches, and half a percent does not pay for a second compute stream's risk
-_BRANCH_ON = __import__("os").environ.get("DGMR_BRANCH_STREAM", "0") != "0"
-
-
-def branch_stream(dev):
-    """A second compute stream for an independent branch of the forward (the temporal discriminator beside the spatial one); autograd
-    runs the branch's backward on it as well.  None: disabled."""
-    if not _BRANCH_ON:
-        return None
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _BRANCH_STREAMS.get(idx)
-    if st is None:
-        st = _BRANCH_STREAMS[idx] = torch.cuda.Stream(device=dev)
-    return st
+def _device_index(dev) -> int:
+    return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
 def join_side_streams():
-    """The current stream waits for everything issued on the weight-gradient streams and on the branch stream (no host
-    synchronisation): parameter gradients are written by the kernels, not handed to autograd, so its own end-of-backward stream
-    synchronisation does not cover them."""
-    flush_deferred()
+    """The current stream waits for everything issued on its device's weight-gradient stream (no host synchronisation): parameter
+    gradients are written by the kernels, not handed to autograd, so its own end-of-backward stream synchronisation does not
+    cover them."""
     cur = torch.cuda.current_stream()
-    _tail_end_of_pass(cur, [side for (idx, _lane), side in _SIDE_STREAMS.items() if cur.device.index == idx])
-    for idx, st in _BRANCH_STREAMS.items():
-        if cur.device.index == idx:
-            cur.wait_stream(st)
-    for (idx, _lane), side in _SIDE_STREAMS.items():
-        if cur.device.index == idx:
-            cur.wait_stream(side)
+    side = _SIDE_STREAMS.get(cur.device.index)
+    _tail_end_of_pass(cur, side)
+    if side is not None:
+        cur.wait_stream(side)
     _SIDE_PENDING.clear()
     _SIDE_KEEP.clear()
 
 
 def _join_side_streams():
-    flush_deferred()  # (end of a backward pass: nothing may stay behind)
     if _DEFER_JOIN[0]:
         return
     if _SIDE_PENDING:
-        key0, main0 = next(iter(_SIDE_PENDING.items()))
-        _tail_end_of_pass(main0, [_SIDE_STREAMS[k] for k in _SIDE_PENDING])
-    for key, main in list(_SIDE_PENDING.items()):
-        main.wait_stream(_SIDE_STREAMS[key])
-    for idx, st in _BRANCH_STREAMS.items():  # (its own parameter gradients; the default stream is the one readers use)
-        torch.cuda.default_stream(torch.device("cuda", idx)).wait_stream(st)
-        for (i2, _lane), side in _SIDE_STREAMS.items():
-            if i2 == idx:
-                torch.cuda.default_stream(torch.device("cuda", idx)).wait_stream(side)
+        idx0, main0 = next(iter(_SIDE_PENDING.items()))
+        _tail_end_of_pass(main0, _SIDE_STREAMS[idx0])
+    for idx, main in list(_SIDE_PENDING.items()):
+        main.wait_stream(_SIDE_STREAMS[idx])
     _SIDE_PENDING.clear()
     _SIDE_KEEP.clear()  # everything the main stream does from here on is ordered behind the side work
-
-
-# Deferred weight gradients (DGMR_WGRAD_DEFER=1, inside `with defer_wgrads():` = the generator's backward pass): instead of starting
-# beside the fat data-gradient convs of the G-blocks (both compute-bound: they take CUs from each other, the main chain measured
-# ~14 % slower), the weight gradients of a sampler level are held back until the level's ConvGRU starts its backward-through-time
-# chain - small, latency-bound launches that leave most of the chip idle - and are flushed onto the side stream there
-# (ops.ConvGRUFn.backward calls flush_deferred()).  Whatever is still held when a join happens is flushed first.
-_DEFER_ON = __import__("os").environ.get("DGMR_WGRAD_DEFER", "0") != "0"
-_DEFER_OPEN = [0]
-_DEFERRED = []
-
-
-class defer_wgrads:
-    def __enter__(self):
-        _DEFER_OPEN[0] += 1
-
-    def __exit__(self, exc_type, exc, tb):
-        _DEFER_OPEN[0] -= 1
-        if not _DEFER_OPEN[0]:
-            if exc_type is not None:
-                _DEFERRED.clear()  # the backward pass died: its held-back weight gradients are not wanted (and their operands may be stale)
-            else:
-                flush_deferred()
-
-
-def flush_deferred():
-    if not _DEFERRED:
-        return
-    todo = list(_DEFERRED)
-    _DEFERRED.clear()
-    for dev, fn, tensors, lane in todo:
-        _on_side_stream(dev, fn, tensors, lane, _now=True)
 
 
 # Tail balancing (round 6).  The weight-gradient stream runs behind the data-gradient chain all through a backward pass; when the chain
@@ -129,7 +68,7 @@ def flush_deferred():
 # the wait is MEASURED (two events: the main stream reaching the join, the side stream running dry) and the pass's inline budget moves by
 # half of it - a few steps to settle, no model of kernel speeds.  Same kernels, same operands, same order of gradient-buffer touches:
 # results are bit-identical wherever a call runs.  DGMR_WGRAD_TAIL=0 switches it off.
-_TAIL_ON = __import__("os").environ.get("DGMR_WGRAD_TAIL", "1") != "0"
+_TAIL_ON = os.environ.get("DGMR_WGRAD_TAIL", "1") != "0"
 _TAIL_KEY = 4  # a pass is keyed by the costs of its first calls
 
 
@@ -165,12 +104,13 @@ def tail_stats():
     return out
 
 
-def _tail_inline(cost: float, lane) -> bool:
-    """Called for every weight-gradient job: True = run it on the current (main) stream."""
+def _tail_inline(cost: float, inline_ok: bool) -> bool:
+    """Called for every weight-gradient job: True = run it on the current (main) stream.  inline_ok=False: the job may use a scratch
+    buffer that the side stream's jobs share (stream order is what protects it): it never leaves that stream."""
     ps = _tail_pass
     i = len(ps.costs)
     ps.costs.append(float(cost))
-    if not _TAIL_ON or lane is not None or i < _TAIL_KEY:  # (fixed-lane work shares scratch with its lane: it stays there)
+    if not _TAIL_ON or not inline_ok or i < _TAIL_KEY:
         return False
     pr = _tail_profiles.get(tuple(ps.costs[:_TAIL_KEY]))
     if pr is None or i >= len(pr.costs) or pr.costs[i] != ps.costs[i]:
@@ -181,11 +121,11 @@ def _tail_inline(cost: float, lane) -> bool:
     return False
 
 
-def _tail_end_of_pass(main, sides):
+def _tail_end_of_pass(main, side):
     """At a join, BEFORE the main stream is made to wait: close the pass, read the previous measurement of its profile, start a new one."""
     global _tail_pass
     ps, _tail_pass = _tail_pass, _TailPass()
-    if not _TAIL_ON or len(ps.costs) <= _TAIL_KEY or not sides:
+    if not _TAIL_ON or len(ps.costs) <= _TAIL_KEY or side is None:
         return
     key = tuple(ps.costs[:_TAIL_KEY])
     pr = _tail_profiles.get(key)
@@ -204,32 +144,20 @@ def _tail_end_of_pass(main, sides):
     pr.costs = list(ps.costs)
     ev_main, ev_side = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev_main.record(main)
-    ev_side.record(sides[0])
+    ev_side.record(side)
     pr.pending = (ev_main, ev_side, ps.first_ev, sum(ps.costs) - ps.inline_cost)
 
 
-_SIDE_LANES = int(__import__("os").environ.get("DGMR_WGRAD_LANES", "1"))  # more lanes measured no gain (1051-1060 ms for 1, 2, 3)
-_side_rr = [0]
-
-
-def _on_side_stream(dev, fn, tensors, lane=None, _now=False, cost=0.0):
-    """Run fn() (kernel launches through _stream()) on one of the device's side streams, ordered after everything issued so far on
+def _on_side_stream(dev, fn, tensors, inline_ok=True, cost=0.0):
+    """Run fn() (kernel launches through _stream()) on the device's weight-gradient stream, ordered after everything issued so far on
     the current stream; `tensors`: what fn reads that the caller may free right after (kept alive for the side stream's work).
-    lane: a fixed stream for work that shares a scratch buffer (the pair-sum planes: lane 0); None: round robin.
-    cost: the job's multiply-adds - the tail balancer (above) runs the last jobs of a pass on the current stream instead."""
-    if _DEFER_ON and _DEFER_OPEN[0] and not _now:
-        _DEFERRED.append((dev, fn, tensors, lane))  # (the closure and `tensors` keep every operand alive until the flush)
-        torch.autograd.Variable._execution_engine.queue_callback(_join_side_streams)
-        return
-    if not _now and _tail_inline(cost, lane):
+    cost: the job's multiply-adds - the tail balancer (above) runs the last jobs of a pass on the current stream instead, unless
+    inline_ok=False (see _tail_inline)."""
+    if _tail_inline(cost, inline_ok):
         fn()  # on the main stream, behind the chain: nothing to order, nothing to keep alive
         torch.autograd.Variable._execution_engine.queue_callback(_join_side_streams)
         return
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    if lane is None:
-        _side_rr[0] = (_side_rr[0] + 1) % _SIDE_LANES
-        lane = _side_rr[0]
-    idx = (idx, lane)
+    idx = _device_index(dev)
     main = torch.cuda.current_stream(dev)
     side = _SIDE_STREAMS.get(idx)
     if side is None:
@@ -256,7 +184,6 @@ def _on_side_stream(dev, fn, tensors, lane=None, _now=False, cost=0.0):
 
 
 def side_streams(device) -> List["torch.cuda.Stream"]:
-    """The weight-gradient / branch streams of `device` that exist so far (ddp: a collective must be ordered behind them)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    return [st for (i, _lane), st in _SIDE_STREAMS.items() if i == idx] + [st for i, st in _BRANCH_STREAMS.items() if i == idx]
-
+    """The weight-gradient stream of `device` if it exists so far (ddp: a collective must be ordered behind it)."""
+    side = _SIDE_STREAMS.get(_device_index(device))
+    return [] if side is None else [side]

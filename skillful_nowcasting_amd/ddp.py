@@ -247,9 +247,9 @@ class GradSync:
         if piece.is_cuda:
             from . import ops
 
-            # a touch may fire on the weight-gradient stream (grad_buffer() inside weight_grad()) or, with DGMR_BRANCH_STREAM=1, on the
-            # branch stream: order the collective behind the stream begin() was called on, the CURRENT one, the device's default
-            # stream and every side stream - whichever of them carries kernels that write this bucket
+            # a touch may fire on the weight-gradient stream (grad_buffer() inside the weight-gradient job): order the collective
+            # behind the stream begin() was called on, the CURRENT one, the device's default stream and the weight-gradient
+            # stream - whichever of them carries kernels that write this bucket
             main = torch.cuda.current_stream(piece.device)
             if self._comm_stream is None:
                 self._comm_stream = torch.cuda.Stream(device=piece.device)
@@ -317,11 +317,7 @@ class GradSync:
         # values; the pass state is committed only on success - a caller that catches the error and goes on keeps exchanging
         # un-overlapped, back to front, which pairs by bucket index on every rank
         if self.exchange:
-            # (seeded with the one process-level switch that moves the touch order - DGMR_WGRAD_DEFER fires the gradient-buffer touches at
-            #  flush time: ranks that disagree on it must not overlap)
-            from . import _streams
-
-            h = 7 if _streams._DEFER_ON else 0
+            h = 0
             for b in order:
                 h = (h * 1000003 + b + 1) % 2147483629
             t = torch.tensor([h, -h], dtype=torch.int64, device=fg.flat.device if fg.flat.is_cuda else "cpu")

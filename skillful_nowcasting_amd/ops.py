@@ -15,26 +15,26 @@ epilogue fuse the spectral-norm chain rule and skips autograd's separate accumul
 from __future__ import annotations
 
 import ctypes
+import os
 import weakref
-from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
-from ._lib import ConvArgs, WgradArgs, call
+from ._lib import ConvArgs, WgradArgs, call, load
 
 from . import _core, _streams
 from ._core import (BNState, CallLayout, SNCall, SPLITK_WS_BYTES, _copy, _dims, _p, _scratch, _splitk_ws, _stream, bn_prepare,  # noqa: F401
                     bias_rows, bump_weights_epoch, call_slots, deterministic, dot_buffer, empty_cl, grad_buffer, require_hip,
-                    require_weight_layout, set_deterministic, set_grad_touch_hook, sums_buffer, colsum_tmp, to_cl, upload, weights_epoch)
+                    require_weight_layout, set_deterministic, set_grad_touch_hook, sums_buffer, colsum_tmp, to_cl, upload)
 from ._head_ops import (AttentionFn, AxpbyFn, BatchNorm1dFn, GridCellFn, HingeDiscFn, MeanFn, ReluSumHWFn, SNLinear1Fn, adam_update,  # noqa: F401
                         attention, axpby, relu_sum_hw)
 from ._layout_ops import (CatChannelsFn, D2SFramesFn, FramesS2DFn, FramesToBatchFn, PoolAddFn, RepeatBatchFn, StackBatchFn,  # noqa: F401
                           SumGroupsFn, TimeToChannelsFn, UnstackBatchFn, avg_pool_add, cat_channels, d2s_frames, frames_s2d,
                           frames_to_batch, repeat_batch, stack_batch, sum_groups, time_to_channels, unstack_batch)
-from ._streams import (_on_side_stream, branch_stream, defer_side_join, defer_wgrads, flush_deferred, join_side_streams,  # noqa: F401
-                       side_streams)
+from ._streams import _on_side_stream, defer_side_join, join_side_streams, side_streams  # noqa: F401
 
 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16x6": 3}
@@ -47,6 +47,13 @@ _PLANES = {0: 0, 1: 2, 2: 2, 3: 3}  # bf16 planes per pre-split weight tensor in
 # amplified that way (the BatchNorm1d backward itself is exact fp32 VALU arithmetic on the forward's features).
 _ALIASES = {"mixed": ("bf16x3", "bf16x6")}
 _D_FORWARD_CODE = None  # precision code of the discriminator forward, None: the global mode
+_PRECISION_CODE = 0  # mirror of the library's mode (set_precision keeps it in sync): 0 means no pre-split weights are needed
+
+# Environment switches, read once at import.  Tests and tools assign these module attributes: the code below reads them at call time.
+_WGRAD_STREAM = os.environ.get("DGMR_WGRAD_STREAM", "1") != "0"  # weight gradients on a second stream beside the data-gradient chain (_streams.py)
+_GRU_FUSE_GATES = os.environ.get("DGMR_GRU_FUSE", "1") != "0"  # measurement switch
+_NO_PHASES = bool(int(os.environ.get("DGMR_NO_PHASES", "0")))  # measurement switch (tools/conv_bench.py)
+_UP_WGRAD_SUMS = bool(int(os.environ.get("DGMR_UP_WGRAD_SUMS", "0")))  # A/B switch: pair-sum weight gradient of upsampling convs everywhere
 
 
 def _set_code(code: int):
@@ -76,8 +83,6 @@ def set_precision(mode: str, discriminator_forward: Optional[str] = None):
 
 
 def get_precision() -> str:
-    from ._lib import load
-
     code = int(load().dgmr_get_precision())
     name = next(k for k, v in PRECISIONS.items() if v == code)
     if _D_FORWARD_CODE is not None:
@@ -100,15 +105,6 @@ class discriminator_forward_precision:
     def __exit__(self, *exc):
         if self.prev is not None:
             _set_code(self.prev)
-
-
-# Weight gradients off the critical path: the backward chain only needs each conv's DATA gradient; its weight gradient (window /
-# im2col kernel, slab reduce, spectral-norm finalize - latency-bound kernels at 20-30 % matrix-pipe occupancy) runs on a second
-# stream beside the data-gradient convs of the layers below.  The main stream joins it when the backward pass ends
-# (autograd engine callback), i.e. before anything can read a .grad.
-_WGRAD_STREAM = __import__("os").environ.get("DGMR_WGRAD_STREAM", "1") != "0"
-
-_GRU_KEEP_ALWAYS = bool(int(__import__("os").environ.get("DGMR_GRU_KEEP_ALWAYS", "0")))  # measurement switch
 
 
 def spectral_sigma(w: torch.Tensor, u: torch.Tensor, v: torch.Tensor, scratch: torch.Tensor, eps: float, train: bool) -> SNCall:
@@ -178,7 +174,27 @@ class ConvSpec:
         return self.sn.groups if self.sn is not None else 1
 
 
-_flip_cache = {}
+def _kdims(w: torch.Tensor):
+    ks = list(w.shape[2:])
+    return tuple([1] + ks) if len(ks) == 2 else tuple(ks)
+
+
+# Derived images of weights (flipped tensors, bf16 planes, phase / pooled tap sums), kept until a parameter they were made from changes.
+_weight_images = {}  # (kind, ids of the parameters, *what else selects the image) -> (tags, image, weakrefs of the parameters)
+
+
+def _weight_image(kind: str, ws: Sequence[torch.Tensor], extra: tuple, build):
+    """THE cache protocol of every derived weight image: `build()` makes the image of the parameters `ws`; it is kept while
+    _core.weight_tag of every one of them stands (an optimiser step, an out-of-band write or a new address makes a new tag) and is
+    dropped when any of them is freed.  `kind` keeps the keys of different images of one parameter apart."""
+    key = (kind, tuple(id(w) for w in ws)) + extra
+    tags = tuple(_core.weight_tag(w) for w in ws)
+    hit = _weight_images.get(key)
+    if hit is not None and hit[0] == tags and all(r() is w for r, w in zip(hit[2], ws)):  # (the weakrefs guard against id() reuse)
+        return hit[1]
+    image = build()
+    _weight_images[key] = (tags, image, tuple(weakref.ref(w, lambda _r, k=key: _weight_images.pop(k, None)) for w in ws))
+    return image
 
 
 def _flipped_weight(w: torch.Tensor, coff: int = 0, cin: Optional[int] = None) -> torch.Tensor:
@@ -186,21 +202,14 @@ def _flipped_weight(w: torch.Tensor, coff: int = 0, cin: Optional[int] = None) -
     cout, cin_total = w.shape[0], w.shape[1]
     if cin is None:
         cin = cin_total
-    key = (id(w), coff, cin)
-    tag = _core.weight_tag(w)
-    hit = _flip_cache.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is w:  # the weakref guards against id() reuse after a parameter is freed
-        return hit[1]
-    ks = list(w.shape[2:])
-    kd, kh, kw = ([1] + ks) if len(ks) == 2 else ks
-    wt = torch.empty(cout * cin * kd * kh * kw, device=w.device, dtype=torch.float32)
-    call("dgmr_conv_flip_weights", _p(w), _p(wt), cout, cin, kd, kh, kw, cin_total, coff, _stream())
-    _flip_cache[key] = (tag, wt, weakref.ref(w, lambda _r, k=key: _flip_cache.pop(k, None)))  # freed with the parameter
-    return wt
 
+    def build():
+        kd, kh, kw = _kdims(w)
+        wt = torch.empty(cout * cin * kd * kh * kw, device=w.device, dtype=torch.float32)
+        call("dgmr_conv_flip_weights", _p(w), _p(wt), cout, cin, kd, kh, kw, cin_total, coff, _stream())
+        return wt
 
-_split_cache = {}
-_PRECISION_CODE = 0  # mirror of the library's mode (set_precision keeps it in sync): 0 means no pre-split weights are needed
+    return _weight_image("flip", (w,), (coff, cin), build)
 
 
 def _split_planes(w: torch.Tensor, flipped: bool, coff: int = 0, cin: Optional[int] = None) -> Optional[torch.Tensor]:
@@ -219,21 +228,16 @@ def _split_planes(w: torch.Tensor, flipped: bool, coff: int = 0, cin: Optional[i
     if k_c % 8:
         return None
     planes = _PLANES[_PRECISION_CODE]
-    key = (id(w), flipped, coff, cin, planes)
-    tag = _core.weight_tag(w)
-    hit = _split_cache.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is w:
-        return hit[1]
-    out = torch.empty(planes * cout * taps * cin, device=w.device, dtype=torch.int16)
-    if flipped:  # the flipped slice is already dense
-        call("dgmr_split_weights", _p(_flipped_weight(w, coff, cin)), _p(out), rows_c * taps, k_c, 0, 0, planes, 0, _stream())
-    else:
-        call("dgmr_split_weights", _p(w), _p(out), rows_c * taps, k_c, cin_total, coff, planes, 0, _stream())
-    _split_cache[key] = (tag, out, weakref.ref(w, lambda _r, k=key: _split_cache.pop(k, None)))
-    return out
 
+    def build():
+        out = torch.empty(planes * cout * taps * cin, device=w.device, dtype=torch.int16)
+        if flipped:  # the flipped slice is already dense
+            call("dgmr_split_weights", _p(_flipped_weight(w, coff, cin)), _p(out), rows_c * taps, k_c, 0, 0, planes, 0, _stream())
+        else:
+            call("dgmr_split_weights", _p(w), _p(out), rows_c * taps, k_c, cin_total, coff, planes, 0, _stream())
+        return out
 
-_GRU_FUSE_GATES = __import__("os").environ.get("DGMR_GRU_FUSE", "1") != "0"  # measurement switch
+    return _weight_image("split", (w,), (flipped, coff, cin, planes), build)
 
 
 def _split_planes_cat(ws: Sequence[torch.Tensor], coff: int, cin: int) -> Optional[torch.Tensor]:
@@ -243,25 +247,18 @@ def _split_planes_cat(ws: Sequence[torch.Tensor], coff: int, cin: int) -> Option
     if _PRECISION_CODE == 0 or cin % 8 or any(w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) for w in ws):
         return None
     planes = _PLANES[_PRECISION_CODE]
-    key = (tuple(id(w) for w in ws), "cat", coff, cin, planes)
-    tag = tuple(_core.weight_tag(w) for w in ws)
-    hit = _split_cache.get(key)
-    if hit is not None and hit[0] == tag and all(r() is w for r, w in zip(hit[2], ws)):
-        return hit[1]
-    rows = sum(w.shape[0] for w in ws)
-    stride = rows * 9 * cin
-    out = torch.empty(planes * stride, device=ws[0].device, dtype=torch.int16)
-    r0 = 0
-    for w in ws:
-        call("dgmr_split_weights", _p(w), out.data_ptr() + 2 * r0 * 9 * cin, w.shape[0] * 9, cin, w.shape[1], coff, planes, stride, _stream())
-        r0 += w.shape[0]
-    _split_cache[key] = (tag, out, tuple(weakref.ref(w, lambda _r, k=key: _split_cache.pop(k, None)) for w in ws))
-    return out
 
+    def build():
+        rows = sum(w.shape[0] for w in ws)
+        stride = rows * 9 * cin
+        out = torch.empty(planes * stride, device=ws[0].device, dtype=torch.int16)
+        r0 = 0
+        for w in ws:
+            call("dgmr_split_weights", _p(w), out.data_ptr() + 2 * r0 * 9 * cin, w.shape[0] * 9, cin, w.shape[1], coff, planes, stride, _stream())
+            r0 += w.shape[0]
+        return out
 
-_phase_cache = {}
-_NO_PHASES = bool(int(__import__("os").environ.get("DGMR_NO_PHASES", "0")))  # measurement switch (tools/conv_bench.py)
-_UP_WGRAD_SUMS = bool(int(__import__("os").environ.get("DGMR_UP_WGRAD_SUMS", "0")))  # A/B switch: pair-sum weight gradient of upsampling convs everywhere
+    return _weight_image("cat", tuple(ws), (coff, cin, planes), build)
 
 
 def _phase_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -271,17 +268,15 @@ def _phase_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
         return None
     cout, cin = w.shape[0], w.shape[1]
     planes = _PLANES[_PRECISION_CODE]
-    key = (id(w), "phase", planes)
-    tag = _core.weight_tag(w)
-    hit = _phase_cache.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is w:
-        return hit[1]
-    sums = torch.empty(16 * cout * cin, device=w.device, dtype=torch.float32)
-    call("dgmr_upsample_phase_weights", _p(w), _p(sums), cout, cin, _stream())
-    out = torch.empty(planes * 16 * cout * cin, device=w.device, dtype=torch.int16)
-    call("dgmr_split_weights", _p(sums), _p(out), 16 * cout, cin, 0, 0, planes, 0, _stream())
-    _phase_cache[key] = (tag, out, weakref.ref(w, lambda _r, k=key: _phase_cache.pop(k, None)))
-    return out
+
+    def build():
+        sums = torch.empty(16 * cout * cin, device=w.device, dtype=torch.float32)
+        call("dgmr_upsample_phase_weights", _p(w), _p(sums), cout, cin, _stream())
+        out = torch.empty(planes * 16 * cout * cin, device=w.device, dtype=torch.int16)
+        call("dgmr_split_weights", _p(sums), _p(out), 16 * cout, cin, 0, 0, planes, 0, _stream())
+        return out
+
+    return _weight_image("phase", (w,), (planes,), build)
 
 
 def _pool2_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -291,17 +286,15 @@ def _pool2_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
         return None
     cout, cin = w.shape[0], w.shape[1]
     planes = _PLANES[_PRECISION_CODE]
-    key = (id(w), "pool2", planes)
-    tag = _core.weight_tag(w)
-    hit = _phase_cache.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is w:
-        return hit[1]
-    sums = torch.empty(16 * cout * cin, device=w.device, dtype=torch.float32)
-    call("dgmr_pool2_phase_weights", _p(_flipped_weight(w)), _p(sums), cin, cout, _stream())
-    out = torch.empty(planes * 16 * cout * cin, device=w.device, dtype=torch.int16)
-    call("dgmr_split_weights", _p(sums), _p(out), 16 * cin, cout, 0, 0, planes, 0, _stream())
-    _phase_cache[key] = (tag, out, weakref.ref(w, lambda _r, k=key: _phase_cache.pop(k, None)))
-    return out
+
+    def build():
+        sums = torch.empty(16 * cout * cin, device=w.device, dtype=torch.float32)
+        call("dgmr_pool2_phase_weights", _p(_flipped_weight(w)), _p(sums), cin, cout, _stream())
+        out = torch.empty(planes * 16 * cout * cin, device=w.device, dtype=torch.int16)
+        call("dgmr_split_weights", _p(sums), _p(out), 16 * cin, cout, 0, 0, planes, 0, _stream())
+        return out
+
+    return _weight_image("pool2", (w,), (planes,), build)
 
 
 def _pool2_fwd_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -313,23 +306,16 @@ def _pool2_fwd_planes(w: torch.Tensor) -> Optional[torch.Tensor]:
     cout, cin = w.shape[0], w.shape[1]
     kd = 3 if w.dim() == 5 else 1
     planes = _PLANES[_PRECISION_CODE]
-    key = (id(w), "pool2f", planes)
-    tag = _core.weight_tag(w)
-    hit = _phase_cache.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is w:
-        return hit[1]
-    sums = torch.empty(16 * kd * cout * cin, device=w.device, dtype=torch.float32)
-    call("dgmr_pool2_phase_weights", _p(w), _p(sums), cout * kd, cin, _stream())  # rows (co, kd): [co][kd * 16 + t][ci]
-    call("dgmr_axpby", _p(sums), None, _p(sums), 0.25, 0.0, sums.numel(), _stream())
-    out = torch.empty(planes * sums.numel(), device=w.device, dtype=torch.int16)
-    call("dgmr_split_weights", _p(sums), _p(out), 16 * kd * cout, cin, 0, 0, planes, 0, _stream())
-    _phase_cache[key] = (tag, out, weakref.ref(w, lambda _r, k=key: _phase_cache.pop(k, None)))
-    return out
 
+    def build():
+        sums = torch.empty(16 * kd * cout * cin, device=w.device, dtype=torch.float32)
+        call("dgmr_pool2_phase_weights", _p(w), _p(sums), cout * kd, cin, _stream())  # rows (co, kd): [co][kd * 16 + t][ci]
+        call("dgmr_axpby", _p(sums), None, _p(sums), 0.25, 0.0, sums.numel(), _stream())
+        out = torch.empty(planes * sums.numel(), device=w.device, dtype=torch.int16)
+        call("dgmr_split_weights", _p(sums), _p(out), 16 * kd * cout, cin, 0, 0, planes, 0, _stream())
+        return out
 
-def _kdims(w: torch.Tensor):
-    ks = list(w.shape[2:])
-    return tuple([1] + ks) if len(ks) == 2 else tuple(ks)
+    return _weight_image("pool2f", (w,), (planes,), build)
 
 
 EPI_PLAIN, EPI_GRU_GATE, EPI_GRU_BLEND, EPI_GRU_GATES2 = 0, 1, 2, 3
@@ -366,19 +352,13 @@ def _launch_conv(x, w_ptr, bias, scale, y, n, d, h, w_, cin, cout, kd, kh, kw, *
     a.act_relu = int(act_relu)
     a.pool2 = int(bool(pool2))
     if pool2:
-        from ._lib import load
-
         if not load().dgmr_conv_pool2_supported(ctypes.byref(a)):
             return NotImplemented
     if gates2 is not None:
-        from ._lib import load
-
         if not load().dgmr_conv_gates2_supported(ctypes.byref(a)):
             return NotImplemented
     partials = None
     if want_stats:
-        from ._lib import load
-
         rows = int(load().dgmr_conv_stats_rows(ctypes.byref(a)))
         if rows > 0:
             partials = torch.empty(rows, 2, cout, device=y.device, dtype=torch.float32)
@@ -387,8 +367,171 @@ def _launch_conv(x, w_ptr, bias, scale, y, n, d, h, w_, cin, cout, kd, kh, kw, *
     return partials
 
 
+def _bn_operands(prefix: str, bn: Optional[BNState], a=None, b=None) -> dict:
+    """The `<prefix>_a / _b / _group` keywords of _launch_conv ("pre": BatchNorm+ReLU on the operand load, "mask": its backward on the
+    epilogue) for the BatchNorm in front of a conv; none without one.  `a`, `b`: the saved tensors in a backward pass (see ConvFn._save)."""
+    if bn is None:
+        return {}
+    return {prefix + "_a": bn.a if a is None else a, prefix + "_b": bn.b if b is None else b, prefix + "_group": bn.group_size}
+
+
+def _launch_wgrad(wa: WgradArgs, slab: int, dev, st):
+    """Plan, allocate and launch one weight gradient: `wa` arrives filled but for its outputs; returns (partial, nsplit), `nsplit`
+    slabs of `slab` floats that _reduce_wgrad (or dgmr_wgrad_reduce_slice) sums."""
+    call("dgmr_conv_wgrad_plan", ctypes.byref(wa))  # slab count: depends on which kernel the library will pick
+    ns = wa.nsplit
+    partial = torch.empty(ns * slab, device=dev, dtype=torch.float32)
+    wa.partial = _p(partial)
+    rows_ws = bias_rows(wa, dev)  # deterministic mode: the slabs' bias sums in rows of their own (kept alive past the launch)
+    call("dgmr_conv_wgrad", ctypes.byref(wa), st)
+    del rows_ws
+    return partial, ns
+
+
+def _reduce_wgrad(partial, ns: int, w, scale, sn_uv, scale_param, groups: int, cout: int, cin: int, taps: int, st):
+    """Sum the `ns` slabs of a raw weight gradient and accumulate dW into grad_buffer(w): as it is (no scale), through the spectral-norm
+    chain rule (`sn_uv` = the call's (u, v)), or for a learnable scalar gain (whose own gradient goes to grad_buffer(scale_param))."""
+    dev = w.device
+    n = cout * cin * taps
+    gw = grad_buffer(w)
+    g = torch.empty(n, device=dev, dtype=torch.float32)
+    if scale is None:
+        call("dgmr_wgrad_reduce", _p(partial), ns, 1, n, None, None, _p(g), None, st)
+    else:
+        # g = sum_q P_q / sigma_q ; dot[q] = <P_q, W>   (P_q: raw weight gradient over the rows of call q)
+        dot = dot_buffer(groups, dev)
+        call("dgmr_wgrad_reduce", _p(partial), ns, groups, n, _p(w), _p(scale), _p(g), _p(dot), st)
+        if sn_uv is not None:
+            call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), _p(dot), _p(scale), _p(sn_uv[0]), _p(sn_uv[1]), cout, cin, taps, groups, 1, st)
+            return
+        if scale_param is not None and scale_param.requires_grad:  # learnable scalar gain: d scale = <P, W>, dW = scale * P
+            gs = grad_buffer(scale_param)
+            call("dgmr_axpby", _p(gs), _p(dot), _p(gs), 1.0, 1.0, 1, st)
+    call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), None, None, None, None, cout, cin, taps, 1, 1, st)
+
+
+def _conv_weight_grad(spec: ConvSpec, geom, x, dy, w, bias, scale, scale_param, bn_a, bn_b, sn_u, sn_v):
+    """dW (with the bias gradient riding along, and the scale's chain rule) of one conv, on the current stream - the side stream when
+    run there."""
+    n, cin, cout, d, h, wd, kd, kh, kw = geom
+    st, dev = _stream(), dy.device
+    bn = spec.bn
+    want_bias = bias is not None and bias.requires_grad
+    wa = WgradArgs()
+    wa.pre_a, wa.pre_b = (_p(bn_a), _p(bn_b)) if bn else (None, None)
+    wa.pre_relu, wa.pre_group = int(spec.pre_relu), (bn.group_size if bn else 1)
+    wa.groups = spec.groups
+    # (where the wave-specialised LDS-window weight gradient applies - whole rows of 32 output pixels, or 16-pixel-wide maps -
+    #  it takes the upsampling conv as it is, nearest-2x fused into its loads, at 330 - 350 TF: 2.3 ms for up_g4.first
+    #  against ~20 ms for the sums kernel, which writes a 9-plane map of 4 GB, plus the GEMM over it)
+    window_wgrad = (wd % 32 == 0 and h % 2 == 0) or (wd == 16 and h % 4 == 0)
+    if (spec.upsample and _PRECISION_CODE != 0 and not _NO_PHASES and (kd, kh, kw) == (1, 3, 3) and d == 1
+            and (_UP_WGRAD_SUMS or not window_wgrad)):
+        # upsampling conv, bf16 modes: sum the 2x2 pixels of dy that meet each INPUT pixel under each tap (9 planes), then the
+        # gradient is a 1x1 problem on the low-resolution map - a quarter of the multiply steps (dgmr_upsample_wgrad_sums)
+        z9 = _scratch(n * (h // 2) * (wd // 2) * 9 * cout, dev, "z9")
+        call("dgmr_upsample_wgrad_sums", _p(dy), _p(z9), n, h // 2, wd // 2, cout, st)
+        wa.x, wa.dy = _p(x), _p(z9)
+        wa.N, wa.D, wa.H, wa.W, wa.Cin, wa.Cout = n, 1, h // 2, wd // 2, cin, 9 * cout
+        wa.KD, wa.KH, wa.KW, wa.upsample = 1, 1, 1, 0
+        # bias: the centre-tap plane (ky = kx = 1) holds every pixel of dy exactly once - its column sums ride in the kernel
+        z9_bias = torch.zeros(9 * cout, device=dev, dtype=torch.float32) if want_bias else None
+        wa.bias_grad = _p(z9_bias)
+    else:
+        z9_bias = None
+        wa.x, wa.dy = _p(x), _p(dy)
+        wa.N, wa.D, wa.H, wa.W, wa.Cin, wa.Cout = n, d, h, wd, cin, cout
+        wa.KD, wa.KH, wa.KW, wa.upsample = kd, kh, kw, int(spec.upsample)
+        wa.bias_grad = _p(grad_buffer(bias)) if want_bias else None
+    taps = kd * kh * kw
+    partial, ns = _launch_wgrad(wa, cout * taps * cin, dev, st)
+    if z9_bias is not None:
+        grad_buffer(bias).add_(z9_bias.view(cout, 9)[:, 4])
+    _reduce_wgrad(partial, ns, w, scale, (sn_u, sn_v) if spec.sn is not None else None, scale_param, spec.groups, cout, cin, taps, st)
+
+
+def _conv_data_grad(spec: ConvSpec, geom, x, dy, w, scale, bn_a, bn_b):
+    """Gradient with respect to pre(x) -> x up to a BatchNorm in front: (g, g_sums) with g_sums the per-tile (sum g, sum g * x) of
+    BatchNorm's backward reduction where the kernel's epilogue delivered them, else None."""
+    n, cin, cout, d, h, wd, kd, kh, kw = geom
+    bn = spec.bn
+    wt = _flipped_weight(w)
+    scale_group = n // spec.groups
+    mask = dict(mask_src=x if (bn or spec.pre_relu) else None, **_bn_operands("mask", bn, bn_a, bn_b))
+    g_sums = NotImplemented
+    if spec.upsample:
+        # flipped conv at full resolution, then the 2x2 window sum (nearest-2x backwards): one pass over the parity planes of dy
+        w_pool = _pool2_planes(w)
+        if w_pool is not None:
+            g = empty_cl(x.shape, dy)
+            g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw, **mask, scale_group=scale_group,
+                                  w_split=_split_planes(w, True), w_phase=w_pool, pool2=True, want_stats=bn is not None)
+    if g_sums is not NotImplemented:
+        pass
+    elif spec.upsample:
+        g_sums = None
+        hi = empty_cl((n, cin, h, wd) if x.dim() == 4 else (n, cin, d, h, wd), dy)
+        _launch_conv(dy, _p(wt), None, scale, hi, n, d, h, wd, cout, cin, kd, kh, kw, scale_group=scale_group,
+                     w_split=_split_planes(w, True))
+        g = empty_cl(x.shape, dy)
+        call("dgmr_pool_fwd", _p(hi), None, _p(g), n, d, h, wd, cin, 1, 1.0, _p(mask["mask_src"]), _p(bn_a) if bn else None,
+             _p(bn_b) if bn else None, bn.group_size if bn else 1, _stream())
+    else:
+        g = empty_cl(x.shape, dy)
+        # behind a BatchNorm the epilogue also leaves per-tile (sum g, sum g * x): BatchNorm's backward reduction
+        g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw, **mask, scale_group=scale_group,
+                              w_split=_split_planes(w, True), want_stats=bn is not None)
+    return g, g_sums
+
+
+def _conv_bn_backward(bn: BNState, x, g, g_sums, bn_mean, bn_rstd):
+    """Backward of the BatchNorm(+ReLU, already applied to g by the mask) in front of a conv: dx, and d gamma / d beta into their buffers."""
+    st, dev = _stream(), g.device
+    c = x.shape[1]
+    r = x.numel() // (c * bn.groups)
+    from_partials = g_sums is not None and g_sums.shape[0] % bn.groups == 0
+    sums = sums_buffer(bn.groups, r, c, dev, row_blocks=not from_partials)
+    if from_partials:
+        call("dgmr_bn_partial_reduce", _p(g_sums), _p(sums), bn.groups, g_sums.shape[0] // bn.groups, c, st)
+        call("dgmr_bn_bwd_center", _p(sums), _p(bn_mean), _p(bn_rstd), bn.groups, c, st)
+    else:
+        call("dgmr_bn_bwd_reduce", _p(g), _p(x), _p(bn_mean), _p(bn_rstd), _p(sums), bn.groups, r, c, st)
+    dx = empty_cl(x.shape, g)
+    dgam = grad_buffer(bn.gamma) if (bn.gamma is not None and bn.gamma.requires_grad) else None
+    dbet = grad_buffer(bn.beta) if (bn.beta is not None and bn.beta.requires_grad) else None
+    call("dgmr_bn_bwd_apply", _p(g), _p(x), _p(bn_mean), _p(bn_rstd), _p(bn.gamma), _p(sums), None, _p(dx), _p(dgam),
+         _p(dbet), bn.groups, r, c, int(bn.train), st)
+    return dx
+
+
+def _conv_residual_grad(spec: ConvSpec, geom, dy, dy_pooled):
+    """Gradient handed to the residual input: dy at the resolution the residual was added at."""
+    n, _cin, cout, _d, h, wd = geom[:6]
+    if dy_pooled is not None:
+        return dy_pooled
+    if not spec.residual_up:
+        return dy
+    d_res = empty_cl((n, cout, h // 2, wd // 2), dy)  # backward of the nearest-2x upsample: sum over the 2x2 window
+    call("dgmr_pool_fwd", _p(dy), None, _p(d_res), n, 1, h, wd, cout, 1, 1.0, None, None, None, 1, _stream())
+    return d_res
+
+
 class ConvFn(Function):
     """y = conv(pre(x), W) * scale + bias (+ residual), pre in {id, relu, BN+relu, nearest-2x∘those}."""
+
+    @staticmethod
+    def _save(ctx, spec: ConvSpec, geom, x, w, bias, scale, has_residual: bool, y_act):
+        bn, sn = spec.bn, spec.sn
+        ctx.spec = spec  # flags only are read from it in backward; its tensors are re-read from saved_tensors
+        ctx.has_residual = has_residual
+        # parameters are kept as-is (checkpointing hands back DETACHED copies of saved tensors: .grad must land on the real ones)
+        ctx.params = (w, bias, scale if spec.gamma_scale else None)
+        # Every tensor the backward reads goes through save_for_backward: under activation checkpointing
+        # (dgmr/dgmr.py:150,176) the saved tensors are replaced by those of the RECOMPUTED forward, whose sigma / u / v
+        # and BatchNorm statistics differ from the first forward's (SURVEY.md Q7); a tensor stashed on ctx would not be.
+        ctx.save_for_backward(x, scale, y_act, sn.u if sn else None, sn.v if sn else None,
+                              bn.a if bn else None, bn.b if bn else None, bn.mean if bn else None, bn.rstd if bn else None)
+        ctx.geom = geom
 
     @staticmethod
     def forward(ctx, x, w, bias, scale, residual, bn_gamma, bn_beta, spec: ConvSpec):
@@ -403,12 +546,12 @@ class ConvFn(Function):
         if w.shape[1] != cin:
             raise RuntimeError(f"conv: input has {cin} channels, weight expects {w.shape[1]}")
         oshape = (n, cout, h, wd) if x.dim() == 4 else (n, cout, d, h, wd)
-        bn = spec.bn
         groups = spec.groups
         if n % groups:
             raise RuntimeError(f"conv: batch {n} is not divisible into {groups} spectral-norm call groups")
+        geom = (n, cin, cout, d, h, wd, kd, kh, kw)
         if spec.pool_out:
-            return ConvFn._forward_pooled(ctx, x, w, bias, scale, residual, spec, (n, cin, cout, d, h, wd, kd, kh, kw))
+            return ConvFn._forward_pooled(ctx, x, w, bias, scale, residual, spec, geom)
         y = empty_cl(oshape, x)
         if residual is not None:
             residual = to_cl(residual)
@@ -416,21 +559,10 @@ class ConvFn(Function):
             if tuple(residual.shape) != tuple(want):
                 raise RuntimeError(f"conv: residual has shape {tuple(residual.shape)}, expected {tuple(want)}")
         partials = _launch_conv(x, _p(w), bias, scale, y, n, d, h, wd, cin, cout, kd, kh, kw, upsample=spec.upsample,
-                                pre_relu=spec.pre_relu, pre_a=bn.a if bn else None, pre_b=bn.b if bn else None,
-                                pre_group=bn.group_size if bn else 1, residual=residual, act_relu=spec.act_relu,
+                                pre_relu=spec.pre_relu, **_bn_operands("pre", spec.bn), residual=residual, act_relu=spec.act_relu,
                                 scale_group=n // groups, w_split=_split_planes(w, False), residual_up=spec.residual_up,
                                 want_stats=spec.want_stats, w_phase=_phase_planes(w) if spec.upsample else None)
-        ctx.spec = spec  # flags only are read from it in backward; its tensors are re-read from saved_tensors
-        ctx.has_residual = residual is not None
-        # parameters are kept as-is (checkpointing hands back DETACHED copies of saved tensors: .grad must land on the real ones)
-        ctx.params = (w, bias, scale if spec.gamma_scale else None)
-        sn = spec.sn
-        # Every tensor the backward reads goes through save_for_backward: under activation checkpointing
-        # (dgmr/dgmr.py:150,176) the saved tensors are replaced by those of the RECOMPUTED forward, whose sigma / u / v
-        # and BatchNorm statistics differ from the first forward's; a tensor stashed on ctx would not be.
-        ctx.save_for_backward(x, scale, y if spec.act_relu else None, sn.u if sn else None, sn.v if sn else None,
-                              bn.a if bn else None, bn.b if bn else None, bn.mean if bn else None, bn.rstd if bn else None)
-        ctx.geom = (n, cin, cout, d, h, wd, kd, kh, kw)
+        ConvFn._save(ctx, spec, geom, x, w, bias, scale, residual is not None, y if spec.act_relu else None)
         if spec.want_stats:
             if partials is not None:
                 ctx.mark_non_differentiable(partials)
@@ -475,12 +607,7 @@ class ConvFn(Function):
             _launch_conv(x, _p(w), bias, scale, full, n, d, h, wd, cin, cout, kd, kh, kw, pre_relu=spec.pre_relu,
                          scale_group=n // groups, w_split=_split_planes(w, False))
             call("dgmr_pool_fwd", _p(full), _p(residual), _p(y), n, d, h, wd, cout, pd, 0.0, None, None, None, 1, _stream())
-        ctx.spec = spec
-        ctx.has_residual = residual is not None
-        ctx.params = (w, bias, scale if spec.gamma_scale else None)
-        sn = spec.sn
-        ctx.save_for_backward(x, scale, None, sn.u if sn else None, sn.v if sn else None, None, None, None, None)
-        ctx.geom = geom
+        ConvFn._save(ctx, spec, geom, x, w, bias, scale, residual is not None, None)
         return y
 
     @staticmethod
@@ -488,7 +615,8 @@ class ConvFn(Function):
         spec: ConvSpec = ctx.spec
         x, scale, y_act, sn_u, sn_v, bn_a, bn_b, bn_mean, bn_rstd = ctx.saved_tensors
         w, bias, scale_param = ctx.params
-        n, cin, cout, d, h, wd, kd, kh, kw = ctx.geom
+        geom = ctx.geom
+        n, cin, cout, d, h, wd, kd, kh, kw = geom
         dy = to_cl(dy)
         dev = dy.device
         dy_pooled = None
@@ -503,139 +631,31 @@ class ConvFn(Function):
             dy = dz
         m = n * d * h * wd
         k = kd * kh * kw * cin
-        bn = spec.bn
-        st = _stream()
-        # ---- bias: column sums of dy ride along in the weight-gradient kernel; standalone only when W is frozen ----
-        want_bias = bias is not None and bias.requires_grad
-        if want_bias and not w.requires_grad:
-            tmp = colsum_tmp(m, cout, dev)
-            call("dgmr_colsum", _p(dy), _p(grad_buffer(bias)), _p(tmp), m, cout, 1, st)
-        # ---- weight (and scale) ----
-        groups = spec.groups
-        taps = kd * kh * kw
         if w.requires_grad:
             def weight_grad():
-                st = _stream()  # (the side stream when run there)
-                wa = WgradArgs()
-                wa.pre_a, wa.pre_b = (_p(bn_a), _p(bn_b)) if bn else (None, None)
-                wa.pre_relu, wa.pre_group = int(spec.pre_relu), (bn.group_size if bn else 1)
-                wa.groups = groups
-                # (where the wave-specialised LDS-window weight gradient applies - whole rows of 32 output pixels, or 16-pixel-wide maps -
-                #  it takes the upsampling conv as it is, nearest-2x fused into its loads, at 330 - 350 TF: 2.3 ms for up_g4.first
-                #  against ~20 ms for the sums kernel, which writes a 9-plane map of 4 GB, plus the GEMM over it)
-                window_wgrad = (wd % 32 == 0 and h % 2 == 0) or (wd == 16 and h % 4 == 0)
-                if (spec.upsample and _PRECISION_CODE != 0 and not _NO_PHASES and (kd, kh, kw) == (1, 3, 3) and d == 1
-                        and (_UP_WGRAD_SUMS or not window_wgrad)):
-                    # upsampling conv, bf16 modes: sum the 2x2 pixels of dy that meet each INPUT pixel under each tap (9 planes), then the
-                    # gradient is a 1x1 problem on the low-resolution map - a quarter of the multiply steps (dgmr_upsample_wgrad_sums)
-                    z9 = _scratch(n * (h // 2) * (wd // 2) * 9 * cout, dev, "z9")
-                    call("dgmr_upsample_wgrad_sums", _p(dy), _p(z9), n, h // 2, wd // 2, cout, st)
-                    wa.x, wa.dy = _p(x), _p(z9)
-                    wa.N, wa.D, wa.H, wa.W, wa.Cin, wa.Cout = n, 1, h // 2, wd // 2, cin, 9 * cout
-                    wa.KD, wa.KH, wa.KW, wa.upsample = 1, 1, 1, 0
-                    # bias: the centre-tap plane (ky = kx = 1) holds every pixel of dy exactly once - its column sums ride in the kernel
-                    z9_bias = torch.zeros(9 * cout, device=dev, dtype=torch.float32) if want_bias else None
-                    wa.bias_grad = _p(z9_bias)
-                else:
-                    z9_bias = None
-                    wa.x, wa.dy = _p(x), _p(dy)
-                    wa.N, wa.D, wa.H, wa.W, wa.Cin, wa.Cout = n, d, h, wd, cin, cout
-                    wa.KD, wa.KH, wa.KW, wa.upsample = kd, kh, kw, int(spec.upsample)
-                    wa.bias_grad = _p(grad_buffer(bias)) if want_bias else None
-                call("dgmr_conv_wgrad_plan", ctypes.byref(wa))  # slab count: depends on which kernel the library will pick
-                ns = wa.nsplit
-                partial = torch.empty(ns * cout * k, device=dev, dtype=torch.float32)
-                wa.partial = _p(partial)
-                rows_ws = bias_rows(wa, dev)  # deterministic mode: the slabs' bias sums in rows of their own (kept alive past the launch)
-                call("dgmr_conv_wgrad", ctypes.byref(wa), st)
-                del rows_ws
-                if z9_bias is not None:
-                    grad_buffer(bias).add_(z9_bias.view(cout, 9)[:, 4])
-                gw = grad_buffer(w)
-                g = torch.empty(cout * k, device=dev, dtype=torch.float32)
-                if scale is None:
-                    call("dgmr_wgrad_reduce", _p(partial), ns, 1, cout * k, None, None, _p(g), None, st)
-                    call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), None, None, None, None, cout, cin, taps, 1, 1, st)
-                else:
-                    # g = sum_q P_q / sigma_q ; dot[q] = <P_q, W>   (P_q: raw weight gradient over the rows of call q)
-                    dot = dot_buffer(groups, dev)
-                    call("dgmr_wgrad_reduce", _p(partial), ns, groups, cout * k, _p(w), _p(scale), _p(g), _p(dot), st)
-                    if spec.sn is not None:
-                        call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), _p(dot), _p(scale), _p(sn_u), _p(sn_v), cout, cin, taps, groups, 1, st)
-                    else:  # learnable scalar gain: d scale = <P, W>, dW = scale * P
-                        if scale_param is not None and scale_param.requires_grad:
-                            gs = grad_buffer(scale_param)
-                            call("dgmr_axpby", _p(gs), _p(dot), _p(gs), 1.0, 1.0, 1, st)
-                        call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), None, None, None, None, cout, cin, taps, 1, 1, st)
+                _conv_weight_grad(spec, geom, x, dy, w, bias, scale, scale_param, bn_a, bn_b, sn_u, sn_v)
 
             if _WGRAD_STREAM and ctx.needs_input_grad[0]:
-                _on_side_stream(dev, weight_grad, (x, dy, scale, bn_a, bn_b, sn_u, sn_v), lane=0 if spec.upsample else None,
+                # (an upsampling conv's weight gradient may go through the z9 scratch, which the side stream's order protects:
+                #  the tail balancer must not run it on the main stream)
+                _on_side_stream(dev, weight_grad, (x, dy, scale, bn_a, bn_b, sn_u, sn_v), inline_ok=not spec.upsample,
                                 cost=float(m) * k * cout * (4.0 / 9.0 if spec.upsample else 1.0))
             else:
                 weight_grad()
-        # ---- input ----
+        elif bias is not None and bias.requires_grad:
+            # bias: column sums of dy ride along in the weight-gradient kernel; standalone only when W is frozen
+            tmp = colsum_tmp(m, cout, dev)
+            call("dgmr_colsum", _p(dy), _p(grad_buffer(bias)), _p(tmp), m, cout, 1, _stream())
         dx = None
         if ctx.needs_input_grad[0]:
-            wt = _flipped_weight(w)
-            g_sums = NotImplemented
-            if spec.upsample:
-                # flipped conv at full resolution, then the 2x2 window sum (nearest-2x backwards): one pass over the parity planes of dy
-                w_pool = _pool2_planes(w)
-                if w_pool is not None:
-                    g = empty_cl(x.shape, dy)
-                    g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw,
-                                          mask_src=x if (bn or spec.pre_relu) else None, mask_a=bn_a if bn else None,
-                                          mask_b=bn_b if bn else None, mask_group=bn.group_size if bn else 1, scale_group=n // groups,
-                                          w_split=_split_planes(w, True), w_phase=w_pool, pool2=True, want_stats=bn is not None)
-            if g_sums is not NotImplemented:
-                pass
-            elif spec.upsample:
-                g_sums = None
-                hi = empty_cl((n, cin, h, wd) if x.dim() == 4 else (n, cin, d, h, wd), dy)
-                _launch_conv(dy, _p(wt), None, scale, hi, n, d, h, wd, cout, cin, kd, kh, kw, scale_group=n // groups,
-                             w_split=_split_planes(w, True))
-                g = empty_cl(x.shape, dy)
-                call("dgmr_pool_fwd", _p(hi), None, _p(g), n, d, h, wd, cin, 1, 1.0, _p(x) if (bn or spec.pre_relu) else None,
-                     _p(bn_a) if bn else None, _p(bn_b) if bn else None, bn.group_size if bn else 1, st)
-            else:
-                g = empty_cl(x.shape, dy)
-                # behind a BatchNorm the epilogue also leaves per-tile (sum g, sum g * x): BatchNorm's backward reduction
-                g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw,
-                                      mask_src=x if (bn or spec.pre_relu) else None, mask_a=bn_a if bn else None,
-                                      mask_b=bn_b if bn else None, mask_group=bn.group_size if bn else 1, scale_group=n // groups,
-                                      w_split=_split_planes(w, True), want_stats=bn is not None)
-            if bn is None:
-                dx = g
-            else:
-                c = cin
-                r = x.numel() // (c * bn.groups)
-                from_partials = g_sums is not None and g_sums.shape[0] % bn.groups == 0
-                sums = sums_buffer(bn.groups, r, c, dev, row_blocks=not from_partials)
-                if from_partials:
-                    call("dgmr_bn_partial_reduce", _p(g_sums), _p(sums), bn.groups, g_sums.shape[0] // bn.groups, c, st)
-                    call("dgmr_bn_bwd_center", _p(sums), _p(bn_mean), _p(bn_rstd), bn.groups, c, st)
-                else:
-                    call("dgmr_bn_bwd_reduce", _p(g), _p(x), _p(bn_mean), _p(bn_rstd), _p(sums), bn.groups, r, c, st)
-                dx = empty_cl(x.shape, dy)
-                dgam = grad_buffer(bn.gamma) if (bn.gamma is not None and bn.gamma.requires_grad) else None
-                dbet = grad_buffer(bn.beta) if (bn.beta is not None and bn.beta.requires_grad) else None
-                call("dgmr_bn_bwd_apply", _p(g), _p(x), _p(bn_mean), _p(bn_rstd), _p(bn.gamma), _p(sums), None, _p(dx), _p(dgam),
-                     _p(dbet), bn.groups, r, c, int(bn.train), st)
-        d_res = None
-        if ctx.has_residual and dy_pooled is not None:
-            d_res = dy_pooled
-        elif ctx.has_residual:
-            if spec.residual_up:  # backward of the nearest-2x upsample: sum over the 2x2 window
-                d_res = empty_cl((n, cout, h // 2, wd // 2), dy)
-                call("dgmr_pool_fwd", _p(dy), None, _p(d_res), n, 1, h, wd, cout, 1, 1.0, None, None, None, 1, st)
-            else:
-                d_res = dy
+            dx, g_sums = _conv_data_grad(spec, geom, x, dy, w, scale, bn_a, bn_b)
+            if spec.bn is not None:
+                dx = _conv_bn_backward(spec.bn, x, dx, g_sums, bn_mean, bn_rstd)
+        d_res = _conv_residual_grad(spec, geom, dy, dy_pooled) if ctx.has_residual else None
         return dx, None, None, None, d_res, None, None, None
 
 
 def call_nsplit(m: int, cout: int, k: int, groups: int = 1) -> int:
-    from ._lib import load
-
     return int(load().dgmr_conv_wgrad_nsplit(m, cout, k, groups))
 
 
@@ -664,8 +684,6 @@ class HeadFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from ._lib import load
-
         spec: ConvSpec = ctx.spec
         x, scale, sn_u, sn_v, bn_a, bn_b, bn_mean, bn_rstd = ctx.saved_tensors
         w, bias = ctx.params
@@ -681,16 +699,8 @@ class HeadFn(Function):
         call("dgmr_head_bwd_sums", _p(x), _p(bn_a), _p(bn_b), _p(w), _p(scale), _p(dy), _p(bn_part), _p(w_part), _p(b_part), m, ppg, c, st)
         if bias is not None and bias.requires_grad:
             grad_buffer(bias).add_(b_part.sum(0))
-        if w.requires_grad:
-            gw = grad_buffer(w)
-            g = torch.empty(4 * c, device=dev, dtype=torch.float32)
-            if scale is None:
-                call("dgmr_wgrad_reduce", _p(w_part), nblk, 1, 4 * c, None, None, _p(g), None, st)
-                call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), None, None, None, None, 4, c, 1, 1, 1, st)
-            else:
-                dot = dot_buffer(groups, dev)
-                call("dgmr_wgrad_reduce", _p(w_part), nblk, groups, 4 * c, _p(w), _p(scale), _p(g), _p(dot), st)
-                call("dgmr_sn_wgrad_finalize", _p(g), _p(gw), _p(dot), _p(scale), _p(sn_u), _p(sn_v), 4, c, 1, groups, 1, st)
+        if w.requires_grad:  # (_head_applies: a scale here is always a spectral norm's)
+            _reduce_wgrad(w_part, nblk, w, scale, (sn_u, sn_v), None, groups, 4, c, 1, st)
         sums = sums_buffer(groups, nblk // groups, c, dev, row_blocks=False)
         call("dgmr_bn_partial_reduce", _p(bn_part), _p(sums), groups, nblk // groups, c, st)
         call("dgmr_bn_bwd_center", _p(sums), _p(bn_mean), _p(bn_rstd), groups, c, st)
@@ -710,8 +720,6 @@ def _head_applies(x, w, scale, residual, spec: ConvSpec) -> bool:
         return False
     if (spec.sn is not None and spec.sn.groups != bn.groups) or (spec.sn is None and scale is not None):
         return False
-    from ._lib import load
-
     n, c, h, wd = x.shape
     return int(load().dgmr_head_blocks(n * h * wd, bn.group_size * h * wd, c)) > 0
 
@@ -769,6 +777,25 @@ gru_gate = GruGateFn.apply
 gru_blend = GruBlendFn.apply
 
 
+class _GruSteps:
+    """Addressing inside a ConvGRU's step tensors ([T * b, ch, hh, ww], step-major, `draws` draw-major call groups per step): where
+    step t starts, which 1/sigma its convs use and how many samples share one."""
+
+    def __init__(self, b: int, ch: int, hh: int, ww: int, draws: int):
+        self.b, self.bs, self.draws = b, b // draws, draws  # bs: samples per draw = per spectral-norm call group within a step
+        self.n_step = b * ch * hh * ww  # floats per step tensor
+
+    def step_ptr(self, t_: torch.Tensor, t: int) -> int:
+        return t_.data_ptr() + 4 * self.n_step * t
+
+    def scale_ptr(self, sn: SNCall, t: int) -> int:
+        """The `draws` sigmas of step t are consecutive (groups in [step][draw] order); a single sigma serves every step."""
+        return sn.inv_sigma.data_ptr() + (4 * t * self.draws if sn.groups > 1 else 0)
+
+    def sgroup(self, sn: SNCall) -> int:
+        return self.bs if sn.groups > 1 else self.b
+
+
 class ConvGRUFn(Function):
     """A whole ConvGRU layer over T steps (dgmr/layers/ConvGRU.py:57-85,102-111) with hand-written backward-through-time.
 
@@ -808,20 +835,11 @@ class ConvGRUFn(Function):
         if nx != (draws if x_shared else tb) or b % draws or wr.shape[1] != cx + ch or wr.shape[0] != ch:
             raise RuntimeError(f"ConvGRU: x {tuple(x_all.shape)} / h0 {tuple(h0.shape)} / weight {tuple(wr.shape)} do not fit T={T}, "
                                f"draws={draws}{' (shared x)' if x_shared else ''}")
-        bs = b // draws  # samples per draw = samples per spectral-norm call group within a step
+        at = _GruSteps(b, ch, hh, ww, draws)
+        step_ptr, scale_ptr, sgroup, n_step, bs = at.step_ptr, at.scale_ptr, at.sgroup, at.n_step, at.bs
         kh, kw = wr.shape[2], wr.shape[3]
         dev = x_all.device
-        n_step = b * ch * hh * ww  # floats per step tensor
         ct = cx + ch
-
-        def step_ptr(t_: torch.Tensor, t: int) -> int:
-            return t_.data_ptr() + 4 * n_step * t
-
-        def scale_ptr(sn: SNCall, t: int) -> int:  # the `draws` sigmas of step t are consecutive (groups in [step][draw] order)
-            return sn.inv_sigma.data_ptr() + (4 * t * draws if sn.groups > 1 else 0)
-
-        def sgroup(sn: SNCall) -> int:
-            return bs if sn.groups > 1 else b
 
         # x parts of the three convs for every step: raw sums (scale and bias are applied with the h part)
         xparts = []
@@ -843,7 +861,7 @@ class ConvGRUFn(Function):
         _copy(_p(h0), _p(buf), n_step)
         # forwards without a graph (the discriminator passes' generator forward, the first pass of the checkpointed draws, eval): the
         # gate pre-activations and r*h of earlier steps are only read by the backward - not stored, one step of scratch instead
-        keep = any(ctx.needs_input_grad) or _GRU_KEEP_ALWAYS
+        keep = any(ctx.needs_input_grad)
         if keep:
             pr, pu, pc, rh = (empty_cl((tb, ch, hh, ww), x_all) for _ in range(4))
         else:
@@ -885,28 +903,19 @@ class ConvGRUFn(Function):
 
     @staticmethod
     def backward(ctx, dout_all):
-        (x_all, buf, pr, pu, pc, rh, isr, ur, vr, isu, uu, vu, isc, uc, vc) = ctx.saved_tensors
+        x_all, buf, pr, pu, pc, rh, *sn_saved = ctx.saved_tensors
         wr, br, wu, bu, wc, bc = ctx.params
         T, b, cx, ch, hh, ww, kh, kw, draws = ctx.geom
-        bs = b // draws
-        gr, gu, gc = ctx.groups
+        at = _GruSteps(b, ch, hh, ww, draws)
+        step_ptr, scale_ptr, sgroup, n_step, bs = at.step_ptr, at.scale_ptr, at.sgroup, at.n_step, at.bs
+        # the three convs' spectral-norm records, rebuilt from the SAVED tensors (checkpointing replaces those, see ConvFn._save)
+        sr, su, sc = (SNCall(*sn_saved[3 * i:3 * i + 3], g_) for i, g_ in enumerate(ctx.groups))
         dout_all = to_cl(dout_all)
         dev = dout_all.device
-        flush_deferred()  # (DGMR_WGRAD_DEFER: the held-back weight gradients of this level's G-blocks start beside the recurrent chain)
         st = _stream()
         tb = T * b
-        n_step = b * ch * hh * ww
         ct = cx + ch
         taps = kh * kw
-
-        def step_ptr(t_: torch.Tensor, t: int) -> int:
-            return t_.data_ptr() + 4 * n_step * t
-
-        def scale_ptr(inv_sigma: torch.Tensor, groups: int, t: int) -> int:
-            return inv_sigma.data_ptr() + (4 * t * draws if groups > 1 else 0)
-
-        def sgroup(groups: int) -> int:
-            return bs if groups > 1 else b
 
         dpr, dpu, dpc = (empty_cl((tb, ch, hh, ww), dout_all) for _ in range(3))
         # scratch of one step each
@@ -924,14 +933,14 @@ class ConvGRUFn(Function):
                 d = step_ptr(dout_all, t)
             call("dgmr_gru_blend_bwd", d, step_ptr(pu, t), hp, step_ptr(pc, t), step_ptr(dpu, t), _p(dh_a), step_ptr(dpc, t), n_step, st)
             # through the candidate conv to r*h, then through the read gate
-            _launch_conv(step_ptr(dpc, t), _p(wt_ch), None, scale_ptr(isc, gc, t), d_rh, b, 1, hh, ww, ch, ch, 1, kh, kw, device=dev,
-                         w_split=sp_ch, scale_group=sgroup(gc))
+            _launch_conv(step_ptr(dpc, t), _p(wt_ch), None, scale_ptr(sc, t), d_rh, b, 1, hh, ww, ch, ch, 1, kh, kw, device=dev,
+                         w_split=sp_ch, scale_group=sgroup(sc))
             call("dgmr_gru_gate_bwd", _p(d_rh), step_ptr(pr, t), hp, step_ptr(dpr, t), _p(dh_b), n_step, st)
             # dh = dh_a + dh_b + convT(dpr / sigma_r, W_rh) + convT(dpu / sigma_u, W_uh)
-            _launch_conv(step_ptr(dpr, t), _p(wt_rh), None, scale_ptr(isr, gr, t), c1, b, 1, hh, ww, ch, ch, 1, kh, kw, residual=dh_a,
-                         device=dev, w_split=sp_rh, scale_group=sgroup(gr))
-            _launch_conv(step_ptr(dpu, t), _p(wt_uh), None, scale_ptr(isu, gu, t), c2, b, 1, hh, ww, ch, ch, 1, kh, kw, residual=c1,
-                         device=dev, w_split=sp_uh, scale_group=sgroup(gu))
+            _launch_conv(step_ptr(dpr, t), _p(wt_rh), None, scale_ptr(sr, t), c1, b, 1, hh, ww, ch, ch, 1, kh, kw, residual=dh_a,
+                         device=dev, w_split=sp_rh, scale_group=sgroup(sr))
+            _launch_conv(step_ptr(dpu, t), _p(wt_uh), None, scale_ptr(su, t), c2, b, 1, hh, ww, ch, ch, 1, kh, kw, residual=c1,
+                         device=dev, w_split=sp_uh, scale_group=sgroup(su))
             call("dgmr_axpby", _p(c2), _p(dh_b), _p(dh_next), 1.0, 1.0, n_step, st)
             have_next = True
         dh0 = None
@@ -954,9 +963,7 @@ class ConvGRUFn(Function):
         def weight_grads():
             st = _stream()  # (the side stream when run there)
             hprev_all = buf  # rows [0, T*B) are h_{-1} .. h_{T-2}
-            for ki, (w, bias, dp, inv_s, u_, v_, g_, hsrc) in enumerate(((wr, br, dpr, isr, ur, vr, gr, hprev_all),
-                                                                         (wu, bu, dpu, isu, uu, vu, gu, hprev_all),
-                                                                         (wc, bc, dpc, isc, uc, vc, gc, rh))):
+            for ki, (w, bias, dp, sn, hsrc) in enumerate(((wr, br, dpr, sr, hprev_all), (wu, bu, dpu, su, hprev_all), (wc, bc, dpc, sc, rh))):
                 m = tb * hh * ww
                 want_bias = bias is not None and bias.requires_grad
                 if not w.requires_grad:
@@ -965,29 +972,22 @@ class ConvGRUFn(Function):
                         call("dgmr_colsum", _p(dp), _p(grad_buffer(bias)), _p(tmpd), m, ch, 1, st)
                     continue
                 g = torch.empty(ch * taps * ct, device=dev, dtype=torch.float32)
-                dot = dot_buffer(g_, dev)
+                dot = dot_buffer(sn.groups, dev)
                 # x half: T*B maps, or (shared x) the T per-step sums against T copies of the one map; h half: always T*B maps
                 x_half = (x_rep, dsum[ki], TD, cx, 0) if x_shared else (x_all, dp, tb, cx, 0)
                 for src, dy, nimg, cin, coff in (x_half, (hsrc, dp, tb, ch, cx)):
-                    k = taps * cin
                     wa = WgradArgs()
                     wa.x, wa.dy = _p(src), _p(dy)
                     wa.N, wa.D, wa.H, wa.W, wa.Cin, wa.Cout = nimg, 1, hh, ww, cin, ch
                     wa.KD, wa.KH, wa.KW = 1, kh, kw
-                    wa.upsample, wa.pre_relu, wa.pre_group, wa.groups = 0, 0, 1, g_
+                    wa.upsample, wa.pre_relu, wa.pre_group, wa.groups = 0, 0, 1, sn.groups
                     wa.bias_grad = _p(grad_buffer(bias)) if (want_bias and coff == 0) else None  # bias gradient once, with the x half
-                    call("dgmr_conv_wgrad_plan", ctypes.byref(wa))
-                    ns = wa.nsplit
-                    partial = torch.empty(ns * ch * k, device=dev, dtype=torch.float32)
-                    wa.partial = _p(partial)
-                    rows_ws = bias_rows(wa, dev)
-                    call("dgmr_conv_wgrad", ctypes.byref(wa), st)
-                    del rows_ws
-                    call("dgmr_wgrad_reduce_slice", _p(partial), ns, g_, ch, taps, cin, ct, coff, _p(w), _p(inv_s), _p(g), _p(dot), st)
-                call("dgmr_sn_wgrad_finalize", _p(g), _p(grad_buffer(w)), _p(dot), _p(inv_s), _p(u_), _p(v_), ch, ct, taps, g_, 1, st)
+                    partial, ns = _launch_wgrad(wa, ch * taps * cin, dev, st)
+                    call("dgmr_wgrad_reduce_slice", _p(partial), ns, sn.groups, ch, taps, cin, ct, coff, _p(w), _p(sn.inv_sigma), _p(g), _p(dot), st)
+                call("dgmr_sn_wgrad_finalize", _p(g), _p(grad_buffer(w)), _p(dot), _p(sn.inv_sigma), _p(sn.u), _p(sn.v), ch, ct, taps, sn.groups, 1, st)
 
         if _WGRAD_STREAM:
-            keep = [buf, rh, dpr, dpu, dpc, x_all, isr, ur, vr, isu, uu, vu, isc, uc, vc]
+            keep = [buf, rh, dpr, dpu, dpc, x_all, *sn_saved]
             if x_shared:
                 keep += [x_rep] + dsum
             _on_side_stream(dev, weight_grads, keep, cost=float(tb * hh * ww) * kh * kw * (cx + ch) * 3 * ch)
@@ -999,22 +999,22 @@ class ConvGRUFn(Function):
             # dx[d] = sum_k convT_k( sum_t dsum_k[t][d] / sigma_k[t][d] ): three convs of ONE map per draw
             dx_all = empty_cl((draws, cx, hh, ww), dout_all)
             tmp = empty_cl((draws, cx, hh, ww), dout_all)
-            chain = ((dsum[0], wr, isr, gr, None, tmp), (dsum[1], wu, isu, gu, tmp, dx_all), (dsum[2], wc, isc, gc, dx_all, tmp))
-            for ds, w, inv_s, g_, res, dst in chain:
+            chain = ((dsum[0], wr, sr, None, tmp), (dsum[1], wu, su, tmp, dx_all), (dsum[2], wc, sc, dx_all, tmp))
+            for ds, w, sn, res, dst in chain:
                 wsum = empty_cl((draws, ch, hh, ww), dout_all)
                 # train: one 1/sigma per (step, draw) = weight [row t][column block d]; eval: a single 1/sigma
-                call("dgmr_group_rowsum", _p(ds), _p(inv_s), _p(wsum), 1, T, draws * n_img, 1 if g_ > 1 else T,
-                     draws if g_ > 1 else 1, st)
+                call("dgmr_group_rowsum", _p(ds), _p(sn.inv_sigma), _p(wsum), 1, T, draws * n_img, 1 if sn.groups > 1 else T,
+                     draws if sn.groups > 1 else 1, st)
                 _launch_conv(wsum, _p(_flipped_weight(w, 0, cx)), None, None, dst, draws, 1, hh, ww, ch, cx, 1, kh, kw, residual=res,
                              w_split=_split_planes(w, True, 0, cx))
             dx_all = tmp
         elif ctx.needs_input_grad[0]:
             dx_all = empty_cl((tb, cx, hh, ww), dout_all)
             tmp = empty_cl((tb, cx, hh, ww), dout_all)
-            chain = ((dpr, wr, isr, gr, None, tmp), (dpu, wu, isu, gu, tmp, dx_all), (dpc, wc, isc, gc, dx_all, tmp))
-            for dp, w, inv_s, g_, res, dst in chain:
-                _launch_conv(dp, _p(_flipped_weight(w, 0, cx)), None, inv_s, dst, tb, 1, hh, ww, ch, cx, 1, kh, kw, residual=res,
-                             scale_group=tb // g_, w_split=_split_planes(w, True, 0, cx))
+            chain = ((dpr, wr, sr, None, tmp), (dpu, wu, su, tmp, dx_all), (dpc, wc, sc, dx_all, tmp))
+            for dp, w, sn, res, dst in chain:
+                _launch_conv(dp, _p(_flipped_weight(w, 0, cx)), None, sn.inv_sigma, dst, tb, 1, hh, ww, ch, cx, 1, kh, kw, residual=res,
+                             scale_group=tb // sn.groups, w_split=_split_planes(w, True, 0, cx))
             dx_all = tmp
         return dx_all, dh0, None, None, None, None, None, None
 

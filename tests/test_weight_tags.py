@@ -55,6 +55,61 @@ def test_global_keying_switch(monkeypatch):
     assert _core.weight_tag(g) != tg
 
 
+def test_weight_image_cache_follows_the_tags_and_the_parameters_lifetime():
+    """ops._weight_image, the one cache of derived weight images: a hit while every parameter's tag stands, one rebuild per optimiser
+    step of a parameter involved or out-of-band epoch, none for a step of another parameter, separate entries per kind, and no entry
+    left behind once a parameter is freed."""
+    import gc
+
+    from skillful_nowcasting_amd import ops
+
+    built = []
+
+    def image_of(kind, ws, extra=()):
+        def build():
+            built.append(kind)
+            return object()
+        return ops._weight_image(kind, ws, extra, build)
+
+    n0 = len(ops._weight_images)
+    w, other = torch.nn.Parameter(torch.zeros(4, 3, 3, 3)), torch.nn.Parameter(torch.zeros(4, 3, 3, 3))
+    _core.note_optimizer_step([w])      # (a tensor no optimiser has written yet would follow the count of ALL steps)
+    _core.note_optimizer_step([other])
+    a = image_of("flip", (w,))
+    assert image_of("flip", (w,)) is a and built == ["flip"], "a second lookup must be a hit"
+    _core.note_optimizer_step([other])
+    assert image_of("flip", (w,)) is a and built == ["flip"], "a step of another parameter must not rebuild"
+    _core.note_optimizer_step([w])
+    b = image_of("flip", (w,))
+    assert b is not a and built == ["flip"] * 2, "a step of the parameter must rebuild, once"
+    assert image_of("flip", (w,)) is b and len(built) == 2
+    _core.bump_weights_epoch()
+    c = image_of("flip", (w,))
+    assert c is not b and len(built) == 3 and image_of("flip", (w,)) is c and len(built) == 3, "an out-of-band epoch must rebuild, once"
+    # two kinds, and two selections of one kind, for the same parameter: separate entries
+    s = image_of("split", (w,))
+    assert s is not c and image_of("flip", (w,)) is c and image_of("split", (w,)) is s and len(built) == 4
+    s8 = image_of("split", (w,), (0, 8))
+    assert s8 is not s and image_of("split", (w,)) is s and len(built) == 5
+    # an image of two parameters: a step of either rebuilds it
+    pair = image_of("cat", (w, other))
+    assert image_of("cat", (w, other)) is pair and len(built) == 6
+    _core.note_optimizer_step([other])
+    pair2 = image_of("cat", (w, other))
+    assert pair2 is not pair and len(built) == 7
+    _core.note_optimizer_step([w])
+    assert image_of("cat", (w, other)) is not pair2 and len(built) == 8
+    assert image_of("flip", (other,)) is not None and len(built) == 9
+    assert len(ops._weight_images) == n0 + 5  # flip(w), split(w), split(w, 0, 8), cat(w, other), flip(other)
+    # freed with the parameter - with ANY of the parameters for a shared image
+    del w
+    gc.collect()
+    assert len(ops._weight_images) == n0 + 1, "entries of a freed parameter stayed in the cache"
+    del other
+    gc.collect()
+    assert len(ops._weight_images) == n0
+
+
 def test_upload_on_cpu_is_a_plain_conversion():
     idx = torch.arange(12, dtype=torch.int64).reshape(3, 4)
     out = _core.upload(idx, "cpu", torch.int32)
