@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DGMR_ABI_VERSION 11
+#define DGMR_ABI_VERSION 12
 
 int dgmr_abi_version(void);
 const char* dgmr_last_error(void);
@@ -114,7 +114,14 @@ typedef struct dgmr_conv_args {
     const float* addend2;    /* [M][gru_split], or NULL */
     float* y2;               /* [M][gru_split]: the update gate's pre-activation */
     int32_t gru_split;       /* C: output columns [0, C) are the read gate's, [C, 2C) the update gate's; Cout == 2 C, C % 4 == 0 */
-    int32_t reserved2;
+    /* -- ABI 12 -- */
+    int32_t plan_n;          /* 0, or a multiple of N: choose the kernel as for a batch of plan_n samples (groups scaled alike).  A launch
+                                on part of a batch then runs the tile variant, window plan and split-K factor - hence the summation order
+                                of every output element - that the same samples get inside the whole batch.  Every chip-fill heuristic
+                                (window kernel or implicit GEMM, tile width, 256-pixel tiles, streaming 1x1, split-K factor and its
+                                workspace cap) reads plan_n; structural requirements (two-image tiles of 8x8 maps: even N and even
+                                scale / pre / mask groups) keep reading N, and where one holds for plan_n but not for N the call fails
+                                with an argument error naming it - no other kernel is picked. */
 } dgmr_conv_args;
 
 /* ---- the sampler's output layer: relu(BatchNorm(x)) -> 1x1 conv to 4 channels (generators.py:159-166), streaming fp32 kernels ----
@@ -143,6 +150,12 @@ int dgmr_head_bwd_apply(const float* x, const float* a, const float* b, const fl
 int dgmr_upsample_wgrad_sums(const float* dy, float* z, int N, int H, int W, int C, void* stream);
 /* 1 when dgmr_conv_fwd accepts these arguments with pool2 = 1 (host arithmetic, no launch). */
 int dgmr_conv_pool2_supported(const dgmr_conv_args* a);
+/* ABI 12: what dgmr_conv_fwd would dispatch for these arguments in the current arithmetic mode - host arithmetic, nothing is launched
+ * and no pointer is dereferenced (pointers count as given / NULL and by their 16-byte alignment).  *detail = the dispatch word of the
+ * profiler records (dgmr_profile_collect_detail: kernel class, tile, 256-pixel tiles, phase / pooled mode, 3-D, split-K ...), *ksplit =
+ * the split-K factor (1: none).  Two argument sets with equal answers run the same kernel with the same reduction order per output
+ * element; with plan_n the answer is that of the whole batch.  < 0 on the argument errors dgmr_conv_fwd would report. */
+int dgmr_conv_plan(const dgmr_conv_args* a, uint32_t* detail, int32_t* ksplit);
 /* out[co][(p*2+q)*4 + a*2+b][ci]: the 4x4 stride-2 kernel of "3x3 conv then 2x2 sum pool" (row u = 2a + 1 - p sums the taps ky with
  * ky + i = u, i in {0,1}), grouped by the parity (p, q) of the input pixel.  w: [Cout][3][3][Cin] fp32; out: [Cout][16][Cin] fp32. */
 int dgmr_pool2_phase_weights(const float* w, float* out, int Cout, int Cin, void* stream);
@@ -363,6 +376,16 @@ int dgmr_frames_s2d(const float* frames, const int32_t* idx, float* out, int B, 
                     int frame_major, int idx_group, void* stream);
 int dgmr_frames_s2d_bwd(const float* dout, const int32_t* idx, float* dframes /* written, every element (ABI 11: gather form, no atomics) */, int B, int T, int C, int H,
                         int W, int F, int pool, int frame_major, int idx_group, void* stream);
+/* ABI 12: the same gather from TWO tensors - output sample n reads the sequence made of the Tc frames of context[n % Bc] ([Bc][Tc][C][H][W])
+ * followed by the Tf frames of following[n % Bf] ([Bf][Tf][C][H][W]); N % Bc == 0, N % Bf == 0; idx selects among the Tc + Tf frames.
+ * torch.cat([images, predictions], dim=1) of dgmr/dgmr.py:186-189 for every generator draw (Bf = N) and the real sequence of every
+ * discriminator call (Bf = Bc) without materialising either; per-element arithmetic is dgmr_frames_s2d's.
+ * _bwd: the gradient of the following frames alone, dfollowing [N][Tf][C][H][W] (Bf == N), written, every element; the context
+ * frames get none. */
+int dgmr_frames_s2d_pair(const float* context, const float* following, const int32_t* idx, float* out, int N, int Bc, int Tc, int Bf,
+                         int Tf, int C, int H, int W, int F, int pool, int frame_major, int idx_group, void* stream);
+int dgmr_frames_s2d_pair_bwd(const float* dout, const int32_t* idx, float* dfollowing, int N, int Tc, int Tf, int C, int H, int W, int F,
+                             int pool, int frame_major, int idx_group, void* stream);
 /* channels-last [B][h][w][4C] -> frames[b][t][c][2h][2w] (PixelShuffle(2)) and its backward. */
 int dgmr_d2s_frames(const float* x, float* frames, int B, int T, int t, int C, int h, int w, void* stream);
 int dgmr_d2s_frames_bwd(const float* dframes, float* dx, int B, int T, int t, int C, int h, int w, void* stream);

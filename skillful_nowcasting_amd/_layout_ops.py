@@ -87,6 +87,81 @@ def frames_s2d(frames, idx=None, pool=False, frame_major=False, as_3d=False, idx
     return FramesS2DFn.apply(frames, idx, pool, frame_major, as_3d, idx_group)
 
 
+class FramesS2DPairFn(Function):
+    """FramesS2DFn on sequences that exist in two pieces: sample i of the `n` outputs is cat(context[i % Bc], following[i % Bf]) along
+    time (dgmr/dgmr.py:186-189: every generator draw, and the real sequence of every discriminator call, share the context frames).
+    Neither the concatenation nor the repeats are materialised; the backward writes the gradient of `following` alone (Bf == n)."""
+
+    @staticmethod
+    def forward(ctx, context, following, idx, n: int, pool: bool, frame_major: bool, as_3d: bool, idx_group: int = 0):
+        require_hip(context)
+        require_hip(following)
+        context, following = context.contiguous(), following.contiguous()
+        bc, tc, c, h, w = context.shape
+        bf, tf = following.shape[:2]
+        if tuple(following.shape[2:]) != (c, h, w) or n % bc or n % bf:
+            raise RuntimeError(f"frames_s2d_pair: {tuple(context.shape)} context and {tuple(following.shape)} following frames do not "
+                               f"make {n} sequences")
+        if idx is not None and idx.dim() == 2:
+            if idx_group < 1 or n % idx_group or idx.shape[0] != n // idx_group:
+                raise RuntimeError(f"frames_s2d_pair: {tuple(idx.shape)} index rows do not fit {n} samples in groups of {idx_group}")
+            f = idx.shape[1]
+        else:
+            idx_group = 0
+            f = tc + tf if idx is None else idx.numel()
+        p = 2 if pool else 1
+        ho, wo = h // (2 * p), w // (2 * p)
+        out = empty_cl((n, 4 * c, f, ho, wo) if as_3d else (n * f, 4 * c, ho, wo), following)
+        call("dgmr_frames_s2d_pair", _p(context), _p(following), _p(idx), _p(out), n, bc, tc, bf, tf, c, h, w, f, int(pool),
+             int(frame_major), idx_group, _stream())
+        ctx.geom = (n, bf, tc, tf, c, h, w, f, int(pool), int(frame_major), idx_group)
+        ctx.idx = idx
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, bf, tc, tf, c, h, w, f, pool, fm, idx_group = ctx.geom
+        if bf != n:
+            raise RuntimeError("frames_s2d_pair: shared following frames take no gradient")
+        dout = to_cl(dout)
+        dfol = torch.empty(n, tf, c, h, w, device=dout.device, dtype=torch.float32)  # (the kernel writes every element)
+        call("dgmr_frames_s2d_pair_bwd", _p(dout), _p(ctx.idx), _p(dfol), n, tc, tf, c, h, w, f, pool, fm, idx_group, _stream())
+        return None, dfol, None, None, None, None, None, None
+
+
+def frames_s2d_pair(context, following, idx=None, n=None, pool=False, frame_major=False, as_3d=False, idx_group: int = 0):
+    return FramesS2DPairFn.apply(context, following, idx, following.shape[0] if n is None else n, pool, frame_major, as_3d, idx_group)
+
+
+class InterleaveHalvesFn(Function):
+    """Two [G*B, ...] row blocks -> [G][first B | second B] rows: the features of the real and of the generated sequences of G
+    discriminator calls, run as two launch sets, in the row order of the joint batch.  Only `second` takes a gradient."""
+
+    @staticmethod
+    def forward(ctx, first, second, groups: int):
+        require_hip(second)
+        first, second = first.contiguous(), second.contiguous()
+        if first.shape != second.shape or first.shape[0] % groups:
+            raise RuntimeError(f"interleave_halves: {tuple(first.shape)} / {tuple(second.shape)} rows in {groups} groups")
+        rows = first.shape[0] // groups
+        out = torch.empty((2 * first.shape[0],) + tuple(first.shape[1:]), device=second.device, dtype=torch.float32)
+        o = out.view(groups, 2, rows, -1)
+        o[:, 0].copy_(first.view(groups, rows, -1))
+        o[:, 1].copy_(second.view(groups, rows, -1))
+        ctx.groups = groups
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g = ctx.groups
+        rows = dout.shape[0] // (2 * g)
+        d = dout.contiguous().view(g, 2, rows, -1)[:, 1].contiguous()
+        return None, d.view((g * rows,) + tuple(dout.shape[1:])), None
+
+
+interleave_halves = InterleaveHalvesFn.apply
+
+
 class D2SFramesFn(Function):
     """T channels-last maps [B,4C,h,w] -> PixelShuffle(2) -> stacked frames [B,T,C,2h,2w] (generators.py:178-181)."""
 

@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DGMR_LIB=<path>: load another build of the library (A/B runs of a compiler flag or an experimental kernel; the tests use the default)
 LIB_PATH = os.environ.get("DGMR_LIB") or os.path.join(_HERE, "lib", "libdgmr_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 P = c_void_p  # every device pointer and the stream travel as void*
 # deterministic mode (fixed-order cross-workgroup sums: bit-identical runs) is the default; DGMR_DETERMINISTIC=0 switches it off (A/B)
@@ -31,7 +31,7 @@ class ConvArgs(Structure):
         ("w_cin", c_int32), ("w_coff", c_int32), ("epi_mode", c_int32), ("ksplit", c_int32),
         ("gru_h", P), ("gru_pu", P), ("pre_out", P), ("splitk_ws", P), ("splitk_ws_bytes", c_int64), ("w_split", P),
         ("residual_up", c_int32), ("reserved0", c_int32), ("stats_out", P), ("w_phase", P), ("pool2", c_int32), ("reserved1", c_int32),
-        ("scale2", P), ("bias2", P), ("addend2", P), ("y2", P), ("gru_split", c_int32), ("reserved2", c_int32),
+        ("scale2", P), ("bias2", P), ("addend2", P), ("y2", P), ("gru_split", c_int32), ("plan_n", c_int32),
     ]
 
 
@@ -103,6 +103,8 @@ SIGNATURES = {
     "dgmr_pool_depth2": [P, P, P, i, i, L, P],
     "dgmr_frames_s2d": [P, P, P, i, i, i, i, i, i, i, i, i, P],
     "dgmr_frames_s2d_bwd": [P, P, P, i, i, i, i, i, i, i, i, i, P],
+    "dgmr_frames_s2d_pair": [P, P, P, P, i, i, i, i, i, i, i, i, i, i, i, i, P],
+    "dgmr_frames_s2d_pair_bwd": [P, P, P, i, i, i, i, i, i, i, i, i, i, P],
     "dgmr_d2s_frames": [P, P, i, i, i, i, i, i, P],
     "dgmr_d2s_frames_bwd": [P, P, i, i, i, i, i, i, P],
     "dgmr_permute_nt": [P, P, i, i, L, P],
@@ -137,6 +139,7 @@ SIGNATURES = {
     "dgmr_head_bwd_sums": [P, P, P, P, P, P, P, P, P, L, L, i, P],
     "dgmr_head_bwd_apply": [P, P, P, P, P, P, P, P, P, P, P, P, P, L, L, i, i, P],
     "dgmr_conv_pool2_supported": [POINTER(ConvArgs)],
+    "dgmr_conv_plan": [POINTER(ConvArgs), POINTER(c_uint32), POINTER(c_int32)],
     "dgmr_split_weights": [P, P, L, i, i, i, i, L, P],
     "dgmr_conv_gates2_supported": [POINTER(ConvArgs)],
     "dgmr_set_precision": [i],

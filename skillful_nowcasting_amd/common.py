@@ -92,22 +92,33 @@ class DBlock(torch.nn.Module):
         self.last_conv_3x3 = conv2d(output_channels, output_channels, 3)
         self.relu = torch.nn.ReLU()
 
-    def forward(self, x: torch.Tensor, calls: int = 1, layout=None) -> torch.Tensor:
+    def draw_sn(self, calls: int = 1, layout=None):
+        """The spectral-norm records of ONE forward of this block (`calls` calls of the reference's), drawn in forward's order: for a
+        batch that runs in parts (`forward(..., sn=records)` on each), so that the state advances once."""
+        if layout is not None:
+            calls = layout.calls
+        convs = (self.conv_1x1, self.first_conv_3x3, self.last_conv_3x3)
+        return tuple(c._sigma(calls, layout) for c in (convs if self.input_channels != self.output_channels else convs[1:]))
+
+    def forward(self, x: torch.Tensor, calls: int = 1, layout=None, sn=None, plan_mult: int = 1) -> torch.Tensor:
         """`calls` > 1: x is a batch of `calls` consecutive calls of this block (one spectral-norm sigma each); `layout`:
-        ops.CallLayout when the groups are not in call order."""
-        kw = dict(calls=calls, layout=layout)
+        ops.CallLayout when the groups are not in call order.  `sn`: records from `draw_sn` (x is then one of `plan_mult` equal parts
+        of the batch they were drawn for)."""
+        kw = dict(calls=calls, layout=layout, plan_mult=plan_mult)
+        sn = tuple(sn) if sn is not None else (None, None, None)
+        sn_1x1, sn_first, sn_last = sn if len(sn) == 3 else (None,) + sn
         if self.input_channels != self.output_channels:
             # shortcut: pool(conv1x1(x)) == conv1x1(pool(x)) (a 1x1 conv acts per pixel, the bias is a constant, pooling is linear),
             # so the 1x1 conv runs on the pooled map: 4x (3-D: 8x) fewer rows, and the pooling pass reads the narrow input
             # instead of the wide output (the reference: dgmr/common.py:222-226; differs by fp32 reassociation only)
-            x1 = self.conv_1x1(x if self.keep_same_output else ops.avg_pool_add(x, None, self._pd), **kw)
+            x1 = self.conv_1x1(x if self.keep_same_output else ops.avg_pool_add(x, None, self._pd), sn=sn_1x1, **kw)
         else:
             x1 = x
-        h = self.first_conv_3x3(x, pre_relu=self.first_relu, **kw)
+        h = self.first_conv_3x3(x, pre_relu=self.first_relu, sn=sn_first, **kw)
         if self.keep_same_output:
-            return self.last_conv_3x3(h, pre_relu=True, residual=x1, **kw)
+            return self.last_conv_3x3(h, pre_relu=True, residual=x1, sn=sn_last, **kw)
         # last conv + pooling + shortcut in one operator (bf16 modes: "3x3 conv, then 2x2 average" as a 4x4 stride-2 pass, ops.ConvFn)
-        return self.last_conv_3x3(h, pre_relu=True, residual=x1, pool_out=True, **kw)
+        return self.last_conv_3x3(h, pre_relu=True, residual=x1, pool_out=True, sn=sn_last, **kw)
 
 
 class LBlock(torch.nn.Module):

@@ -648,20 +648,34 @@ static const bool g_phase_pair = []() {
 }();
 
 // Which LDS-window 3x3 kernel (if any) takes a conv, and with which tiling: shared by the launch and by dgmr_conv_stats_rows.
+// dgmr_conv_args.plan_n: the batch the kernel is chosen for (0: the launch's own N), and how many times the launch's N it is
+static inline int64_t plan_n_of(const dgmr_conv_args& p) { return p.plan_n > 0 ? p.plan_n : p.N; }
+// set by window_plan when a structural requirement holds for the planned batch and fails for the launch's own (dgmr_conv_fwd /
+// dgmr_conv_plan reset it, and refuse the call when it is set: a part of a batch must not silently get another kernel)
+static thread_local const char* g_plan_pin_error = nullptr;
+
 static bool window_plan(const dgmr_conv_args& p, WinPlan* w) {
-    const int64_t M64 = (int64_t)p.N * p.D * p.H * p.W;
+    const int64_t M64 = (int64_t)p.N * p.D * p.H * p.W;          // the launch's own pixels: structural requirements, grids
+    const int64_t Mp = plan_n_of(p) * p.D * p.H * p.W;           // pixels of the planned batch: every chip-fill heuristic
     const int C = p.Cout;
     // 8x8 maps: a tile is two whole images; every per-sample group (1/sigma, BatchNorm statistics, relu mask) must then hold
     // an even number of samples so that a tile never straddles two groups
-    const bool small8 = p.H == 8 && p.W == 8 && p.D == 1 && !p.upsample && p.N % 2 == 0 && (!p.scale || p.scale_group % 2 == 0) &&
-                        (!p.pre_a || p.pre_group % 2 == 0) && (!p.mask_a || p.mask_group % 2 == 0);
+    const auto small8_at = [&](int64_t n, int64_t mul) {
+        return p.H == 8 && p.W == 8 && p.D == 1 && !p.upsample && n % 2 == 0 && (!p.scale || (p.scale_group * mul) % 2 == 0) &&
+               (!p.pre_a || (p.pre_group * mul) % 2 == 0) && (!p.mask_a || (p.mask_group * mul) % 2 == 0);
+    };
+    const bool small8 = small8_at(p.N, 1);
     // the LDS-DMA kernel (both bf16 modes) also takes 3x3x3 convs, plane by plane
     const bool glds_ok = g_precision != 0 && (g_tune_window < 0 || g_tune_window >= 3);
     const bool is3d = p.KD == 3 && p.D > 1 && glds_ok && !p.upsample && !p.residual_up;
-    if (!(g_precision != 0 && p.w_split && ((p.KD == 1 && p.D == 1) || is3d) && p.KH == 3 && p.KW == 3 && p.Cin % 8 == 0 &&
-          (p.W == 16 || p.W % 32 == 0 || small8) &&
-          (g_tune_window < 0 ? (M64 / 128) * ((C + 63) / 64) * (p.reserved0 ? 4 : 1) >= 192 : g_tune_window >= 1)))
-        return false;
+    const auto takes = [&](bool s8) {
+        return g_precision != 0 && p.w_split && ((p.KD == 1 && p.D == 1) || is3d) && p.KH == 3 && p.KW == 3 && p.Cin % 8 == 0 &&
+               (p.W == 16 || p.W % 32 == 0 || s8) &&
+               (g_tune_window < 0 ? (Mp / 128) * ((C + 63) / 64) * (p.reserved0 ? 4 : 1) >= 192 : g_tune_window >= 1);
+    };
+    if (!small8 && p.N > 0 && small8_at(plan_n_of(p), plan_n_of(p) / p.N) && takes(true))
+        g_plan_pin_error = "8x8 maps run in two-image tiles, which need an even N and even scale / pre / mask groups: that holds for plan_n but not for N";
+    if (!takes(small8)) return false;
     w->tw_shift = small8 ? 3 : (p.W == 16 ? 4 : 5);
     w->g_shift = small8 ? 1 : 0;
     w->bnw = C % 128 == 0 ? 128 : (C % 96 == 0 ? 96 : (C <= 64 ? 64 : 128));
@@ -672,13 +686,13 @@ static bool window_plan(const dgmr_conv_args& p, WinPlan* w) {
     if (glds_ok && C <= 8 && C % 4 == 0 && (g_tune_window == 5 || g_tune_window < 0) && g_thin_auto) w->bnw = 16;  // (measured: 1.5 - 1.8 x at 4 and 8 channels, slower at 16)
     // few pixels, many channels (the ConvGRU steps on 8x8 / 16x16 maps: 6144 pixels x 384 channels): 128-column tiles would leave
     // half the CUs without a workgroup - 64-column tiles double the grid (measured 146 -> see profiles/README.md, us per step conv)
-    if (g_tune_window < 0 && C % 64 == 0 && (M64 / 128) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1) < 256) w->bnw = 64;
-    if (g_tune_window < 0 && (M64 / 128) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1) < 192) return false;
+    if (g_tune_window < 0 && C % 64 == 0 && (Mp / 128) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1) < 256) w->bnw = 64;
+    if (g_tune_window < 0 && (Mp / 128) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1) < 192) return false;
     // 256-pixel tiles (8 x 32 or 16 x 16 pixels of one image), LDS-DMA kernel
     // (not at 128 output channels: 8 accumulator blocks per wave spill at two workgroups per CU).  Measured +2 ... +8 % on the
     // 96- / 64-channel layers of the sampler at T x B maps (gpurun r2o), -10 ... -20 % on launches of a few hundred workgroups:
     // automatic only when the 256-pixel tiles still fill the chip four times over
-    const int64_t big_wgs = (M64 / 256) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1);
+    const int64_t big_wgs = (Mp / 256) * ((C + w->bnw - 1) / w->bnw) * (p.reserved0 ? 4 : 1);
     // Wave-specialised persistent kernel (conv_win_ws.h; dgmr_conv_tune window = 7 forces it wherever it applies, -1 takes it when
     // every CU gets a run of items): 2-D, plain epilogue in its 16-byte form, at most ONE fused epilogue operand, 96 / 128-column
     // blocks, 32-bit element offsets, and enough taps per item to hide the previous item's epilogue behind (ws_ups)
@@ -695,7 +709,7 @@ static bool window_plan(const dgmr_conv_args& p, WinPlan* w) {
         int ups = 0;
         for (int u = 1; u <= upsmax && !ups; ++u)
             if ((NU + u - 1) / u + D <= nsl - 1) ups = u;
-        const int64_t items = (M64 / 128) * ((C + w->bnw - 1) / w->bnw) * (mode == 1 ? 4 : 1);
+        const int64_t items = (Mp / 128) * ((C + w->bnw - 1) / w->bnw) * (mode == 1 ? 4 : 1);
         const bool eop_ok = (mode != 1 || (!p.residual && !p.mask_src)) && !(mode == 2 && p.residual);
         if (ups && eop_ok && (g_tune_window == 7 || (g_ws_auto && items >= 4 * (int64_t)num_cus()))) {
             w->ws = true;
@@ -775,11 +789,11 @@ static const bool g_conv1x1 = []() {
     const char* e = getenv("DGMR_CONV1X1");
     return !(e && e[0] == '0');
 }();
-static bool conv1x1_ok(const dgmr_conv_args& p, int64_t M64) {
+static bool conv1x1_ok(const dgmr_conv_args& p, int64_t Mp) {  // Mp: pixels of the planned batch
     return g_conv1x1 && g_tune_variant < 0 && (g_precision == 1 || g_precision == 2) && p.w_split && p.KD == 1 && p.KH == 1 && p.KW == 1 &&
            p.Cin % 8 == 0 && p.Cin >= 32 && p.Cout % 4 == 0 && p.w_cin == p.Cin && p.w_coff == 0 && p.epi_mode == DGMR_EPI_PLAIN && !p.upsample &&
            !p.pool2 && !p.pre_a && !p.addend && !p.residual && !p.mask_src && !p.stats_out && (p.reserved1 & 4) && al16(p.x) &&
-           ((int64_t)p.D * p.H * p.W) % 256 == 0 && M64 / 256 >= 512;  // (enough workgroups to fill the chip twice; tiles inside one sample)
+           ((int64_t)p.D * p.H * p.W) % 256 == 0 && Mp / 256 >= 512;  // (enough workgroups to fill the chip twice; tiles inside one sample)
 }
 static bool stem4_ok(const dgmr_conv_args& p) {
     return g_stem4 && g_tune_variant < 0 && p.Cin == 4 && p.w_cin == 4 && p.w_coff == 0 && p.KH == 3 && p.KW == 3 &&
@@ -827,8 +841,13 @@ extern "C" int dgmr_conv_stats_rows(const dgmr_conv_args* a) {
     return (window_plan(p, &w) && w.glds) ? w.grid_x : 0;
 }
 
-extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
-    DGMR_CHECK_ARG(a && a->x && a->w && a->y, "dgmr_conv_fwd: null pointer");
+// dgmr_conv_fwd (q_detail == nullptr) and dgmr_conv_plan (q_detail given: the dispatch is worked out, reported and NOT launched) in one
+// body, so that the query cannot drift from the launch.  Heuristics read the planned batch (Mp, dgmr_conv_args.plan_n), grids the real one.
+static int conv_dispatch(const dgmr_conv_args* a, void* stream, uint32_t* q_detail, int32_t* q_ksplit) {
+    const bool query = q_detail != nullptr;
+    DGMR_CHECK_ARG(a && (query || (a->x && a->w && a->y)), "dgmr_conv_fwd: null pointer");
+    DGMR_CHECK_ARG(a->plan_n == 0 || (a->N > 0 && a->plan_n >= a->N && a->plan_n % a->N == 0),
+                   "dgmr_conv_fwd: plan_n=%d must be 0 or a multiple of N=%d", a->plan_n, a->N);
     DGMR_CHECK_ARG(a->Cin % 4 == 0 && a->Cin > 0, "dgmr_conv_fwd: Cin=%d must be a positive multiple of 4", a->Cin);
     DGMR_CHECK_ARG(a->Cout > 0, "dgmr_conv_fwd: Cout=%d", a->Cout);
     DGMR_CHECK_ARG((a->KD == 1 || a->KD == 3) && (a->KH == 1 || a->KH == 3) && (a->KW == 1 || a->KW == 3),
@@ -851,6 +870,15 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
                    "dgmr_conv_fwd: DGMR_EPI_GRU_GATES2 needs a conv the LDS-DMA window kernel takes, Cout == 2 * gru_split, gru_split %% 4 == 0, "
                    "gru_h / y2 and 16-byte aligned tensors (ask dgmr_conv_gates2_supported)");
     const int M = (int)M64, Ktot = a->KD * a->KH * a->KW * a->Cin;
+    const int64_t plan_mul = plan_n_of(p) / p.N, Mp = M64 * plan_mul;  // pixels of the planned batch
+    g_plan_pin_error = nullptr;
+#define DGMR_PLAN_DONE(detail_, ksplit_)                                                                              \
+    DGMR_CHECK_ARG(!g_plan_pin_error, "dgmr_conv_fwd: plan_n=%d, N=%d: %s", p.plan_n, p.N, g_plan_pin_error);         \
+    if (query) {                                                                                                      \
+        *q_detail = (detail_);                                                                                        \
+        if (q_ksplit) *q_ksplit = (ksplit_);                                                                          \
+        return 0;                                                                                                     \
+    }
     hipStream_t s = (hipStream_t)stream;
     const int C = a->Cout;
     // Tile choice: N tile from Cout (32x32 MFMA granularity), M tile shrinks when the grid would not fill 256 CUs.
@@ -860,7 +888,7 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
     else if (C % 128 == 0) bn = 128;
     else if (C % 96 == 0) bn = 96;
     else bn = 128;
-    const int64_t wgs128 = ((M64 + 127) / 128) * ((C + bn - 1) / bn);
+    const int64_t wgs128 = ((Mp + 127) / 128) * ((C + bn - 1) / bn);
     const double flops = 2.0 * (double)M64 * (double)Ktot * (double)C;  // algorithmic: 2*MACs of the dense conv
     int variant;
     if (bn == 128) variant = wgs128 >= 256 ? V_F128x128 : V_F64x64;
@@ -875,6 +903,7 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
     // the arithmetic mode (conv_stem4.h)
     if (stem4_ok(p)) {
         const uint32_t detail = 4u | ((p.KD == 3 ? 1u : 0u) << 11);
+        DGMR_PLAN_DONE(detail, 1)
         ProfScope ps(V_F64x64, flops, s, g_precision == 1 ? 1.0 / 3.0 : (g_precision == 3 ? 1.0 / 6.0 : 1.0), detail);
         const int tiles_w = p.W / STEM_TW, tiles_hw = tiles_w * (p.H / STEM_TH);
         const dim3 grid((unsigned)(p.N * p.D * tiles_hw), (unsigned)(p.Cout / STEM_BN));
@@ -884,8 +913,9 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
         return 0;
     }
     // 1x1 convs of the big maps, bf16 / bf16x3: streaming GEMM (conv1x1.h; needs pre-split weights like the window kernels)
-    if (conv1x1_ok(p, M64)) {
+    if (conv1x1_ok(p, Mp)) {
         const uint32_t detail = 5u | ((p.KD == 1 && p.D > 1 ? 1u : 0u) << 11);
+        DGMR_PLAN_DONE(detail, 1)
         ProfScope ps(variant, flops, s, 1.0, detail);
         const int rows = p.D * p.H * p.W;
         if ((g_precision == 1 ? dgmr_tu::launch_conv1x1_ns3(p, M, rows, s) : dgmr_tu::launch_conv1x1_ns1(p, M, rows, s)) != 0) return -1;
@@ -900,10 +930,11 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
                    "dgmr_conv_fwd: stats_out given but the dispatched kernel has no fused statistics (ask dgmr_conv_stats_rows first)");
     if (window_plan(p, &wp)) {
         const int v = wp.bnw == 128 ? V_WIN128 : (wp.bnw == 96 ? V_WIN96 : V_WIN64);
-        const int64_t wgs = (int64_t)wp.grid_x * (phases ? 4 : 1) * ((p.Cout + wp.bnw - 1) / wp.bnw);
+        const int64_t wgs = (int64_t)wp.grid_x * plan_mul * (phases ? 4 : 1) * ((p.Cout + wp.bnw - 1) / wp.bnw);  // (of the planned batch)
         const uint32_t detail = 1u | ((wp.bnw == 48 ? 0u : (wp.bnw == 64 ? 1u : (wp.bnw == 96 ? 2u : (wp.bnw == 128 ? 3u : 4u)))) << 4) | ((wp.big ? 1u : 0u) << 8) |
                                 ((uint32_t)p.reserved0 << 9) | ((p.KD == 3 ? 1u : 0u) << 11) | ((wgs < 1024 ? 1u : 0u) << 12) |
                                 ((wp.glds ? 0u : 1u) << 13) | ((p.epi_mode != DGMR_EPI_PLAIN ? 1u : 0u) << 14);
+        DGMR_PLAN_DONE(detail | ((wp.ws ? 1u : 0u) << 15), 1)
         ProfScope ps(v, flops, s, (phases || p.reserved0 == 2) ? 16.0 / 36.0 : 1.0, detail | ((wp.ws ? 1u : 0u) << 15));
         if (wp.ws) {
             const int64_t items = (int64_t)wp.grid_x * (phases ? 4 : 1) * ((p.Cout + wp.bnw - 1) / wp.bnw);
@@ -925,28 +956,29 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
     if (p.splitk_ws && p.splitk_ws_bytes > 0) {
         const int bm = variant == V_F64x64 ? 64 : 128;
         const int bnv = variant == V_F128x128 ? 128 : (variant == V_F128x96 ? 96 : (variant == V_F128x32 ? 32 : 64));
-        const int64_t wgs = ((M64 + bm - 1) / bm) * ((C + bnv - 1) / bnv);
+        const int64_t wgs = ((Mp + bm - 1) / bm) * ((C + bnv - 1) / bnv);
         const int bk = 32;
         const int nk = (Ktot + bk - 1) / bk;
         if (wgs < 192 && nk >= 8) {
             int64_t S = 512 / wgs;
             if (S > nk / 4) S = nk / 4;
-            const int64_t cap = p.splitk_ws_bytes / ((int64_t)M64 * C * 4);
+            const int64_t cap = p.splitk_ws_bytes / (Mp * C * 4);
             if (S > cap) S = cap;
             if (S > 64) S = 64;
             if (S > 1) p.ksplit = (int)S;
         }
         if (g_tune_ksplit >= 1) {
-            const int64_t cap = p.splitk_ws_bytes / ((int64_t)M64 * C * 4);
+            const int64_t cap = p.splitk_ws_bytes / (Mp * C * 4);
             p.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(g_tune_ksplit, cap), nk));
         }
     }
     {
         const int bm_v = variant == V_F64x64 ? 64 : 128;
         const int bn_v = variant == V_F128x128 ? 128 : (variant == V_F128x96 ? 96 : (variant == V_F128x32 ? 32 : 64));
-        const int64_t wgs_v = ((M64 + bm_v - 1) / bm_v) * ((C + bn_v - 1) / bn_v) * (p.ksplit > 1 ? p.ksplit : 1);
+        const int64_t wgs_v = ((Mp + bm_v - 1) / bm_v) * ((C + bn_v - 1) / bn_v) * (p.ksplit > 1 ? p.ksplit : 1);
         const uint32_t detail = 2u | ((uint32_t)variant << 4) | ((p.ksplit > 1 ? 1u : 0u) << 8) | ((Ktot == p.Cin ? 1u : 0u) << 9) |
                                 ((p.KD == 3 ? 1u : 0u) << 11) | ((wgs_v < 1024 ? 1u : 0u) << 12) | ((p.epi_mode != DGMR_EPI_PLAIN ? 1u : 0u) << 14);
+        DGMR_PLAN_DONE(detail, p.ksplit)
         ProfScope ps(variant, flops, s, 1.0, detail);
         switch (variant) {
             case V_F128x128: launch_conv<V_F128x128, 128, 128, 2, 2>(p, M, Ktot, s); break;
@@ -958,6 +990,14 @@ extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) {
     }
     DGMR_CHECK_LAUNCH();
     return 0;
+#undef DGMR_PLAN_DONE
+}
+
+extern "C" int dgmr_conv_fwd(const dgmr_conv_args* a, void* stream) { return conv_dispatch(a, stream, nullptr, nullptr); }
+
+extern "C" int dgmr_conv_plan(const dgmr_conv_args* a, uint32_t* detail, int32_t* ksplit) {
+    DGMR_CHECK_ARG(detail, "dgmr_conv_plan: null pointer");
+    return conv_dispatch(a, nullptr, detail, ksplit);
 }
 
 extern "C" int dgmr_conv_flip_weights(const float* w, float* w_t, int Cout, int Cin, int KD, int KH, int KW, int w_cin, int w_coff,

@@ -825,8 +825,10 @@ __global__ void pool_bwd_kernel(const float* __restrict__ dy, float* __restrict_
     }
 }
 
+// `fol` given (dgmr_frames_s2d_pair): sample b's sequence is the Tc frames of fr[b % Bc] followed by the T - Tc frames of fol[b % Bf]
 __global__ void frames_s2d_kernel(const float* __restrict__ fr, const int32_t* __restrict__ idx, float* __restrict__ out, int B,
-                                  int T, int C, int H, int W, int F, int p, int frame_major, int idx_group) {
+                                  int T, int C, int H, int W, int F, int p, int frame_major, int idx_group,
+                                  const float* __restrict__ fol, int Bc, int Tc, int Bf) {
     const int Ho = H / (2 * p), Wo = W / (2 * p), Co = 4 * C;
     const int64_t total = (int64_t)B * F * Ho * Wo * Co;
     const float inv = 1.f / (float)(p * p);
@@ -847,7 +849,9 @@ __global__ void frames_s2d_kernel(const float* __restrict__ fr, const int32_t* _
         }
         const int c = co >> 2, dy = (co >> 1) & 1, dx = co & 1;
         const int tf = idx ? idx[(b / idx_group) * F + f] : f;
-        const float* src = fr + (((size_t)b * T + tf) * C + c) * H * W;
+        const float* src = !fol ? fr + (((size_t)b * T + tf) * C + c) * H * W
+                           : (tf < Tc ? fr + (((size_t)(b % Bc) * Tc + tf) * C + c) * H * W
+                                      : fol + (((size_t)(b % Bf) * (T - Tc) + (tf - Tc)) * C + c) * H * W);
         float s = 0.f;
         for (int py = 0; py < p; ++py)
             for (int px = 0; px < p; ++px) s += src[(size_t)((2 * ho + dy) * p + py) * W + (2 * wo + dx) * p + px];
@@ -859,8 +863,9 @@ __global__ void frames_s2d_kernel(const float* __restrict__ fr, const int32_t* _
 // frame order - no atomics, no zero-fill, bit-identical from run to run (the scatter form added duplicates of a randomly drawn
 // frame index in whatever order the workgroups arrived: three draws of one frame among the spatial discriminator's eight happen in
 // ~10 % of the steps).  dframes is WRITTEN, every element.
+// t_off > 0 (dgmr_frames_s2d_pair_bwd): dfr holds frames t_off .. t_off + T - 1 of every sequence only (the frames before get no gradient)
 __global__ void frames_s2d_bwd_kernel(const float* __restrict__ dout, const int32_t* __restrict__ idx, float* __restrict__ dfr,
-                                      int B, int T, int C, int H, int W, int F, int p, int frame_major, int idx_group) {
+                                      int B, int T, int C, int H, int W, int F, int p, int frame_major, int idx_group, int t_off) {
     const int Ho = H / (2 * p), Wo = W / (2 * p), Co = 4 * C;
     const int64_t total = (int64_t)B * T * C * H * W;
     const float inv = 1.f / (float)(p * p);
@@ -871,7 +876,7 @@ __global__ void frames_s2d_bwd_kernel(const float* __restrict__ dout, const int3
         t /= H;
         const int c = t % C;
         t /= C;
-        const int tf = t % T;
+        const int tf = t % T + t_off;
         const int b = t / T;
         const int xo = x / p, yo = y / p;  // pixel of the (pooled) frame
         const int wo = xo >> 1, dx = xo & 1, ho = yo >> 1, dy = yo & 1;
@@ -1835,7 +1840,23 @@ extern "C" int dgmr_frames_s2d(const float* frames, const int32_t* idx, float* o
     DGMR_CHECK_ARG(H % (2 * p) == 0 && W % (2 * p) == 0, "dgmr_frames_s2d: H=%d W=%d not divisible by %d", H, W, 2 * p);
     const int64_t total = (int64_t)B * F * (H / (2 * p)) * (W / (2 * p)) * 4 * C;
     hipLaunchKernelGGL(frames_s2d_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, frames, idx, out, B, T, C, H, W, F, p,
-                       frame_major, idx_group);
+                       frame_major, idx_group, (const float*)nullptr, 0, 0, 0);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_frames_s2d_pair(const float* context, const float* following, const int32_t* idx, float* out, int N, int Bc, int Tc,
+                                    int Bf, int Tf, int C, int H, int W, int F, int pool, int frame_major, int idx_group, void* stream) {
+    if (idx_group < 1) idx_group = N;
+    DGMR_CHECK_ARG(context && following && out, "dgmr_frames_s2d_pair: null pointer");
+    DGMR_CHECK_ARG(N > 0 && Bc > 0 && Bf > 0 && Tc > 0 && Tf > 0 && N % Bc == 0 && N % Bf == 0,
+                   "dgmr_frames_s2d_pair: N=%d must be a multiple of the %d context and the %d following sequences", N, Bc, Bf);
+    DGMR_CHECK_ARG(idx || F <= Tc + Tf, "dgmr_frames_s2d_pair: F=%d frames of a sequence of %d", F, Tc + Tf);
+    const int p = pool ? 2 : 1;
+    DGMR_CHECK_ARG(H % (2 * p) == 0 && W % (2 * p) == 0, "dgmr_frames_s2d_pair: H=%d W=%d not divisible by %d", H, W, 2 * p);
+    const int64_t total = (int64_t)N * F * (H / (2 * p)) * (W / (2 * p)) * 4 * C;
+    hipLaunchKernelGGL(frames_s2d_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, context, idx, out, N, Tc + Tf, C, H, W, F, p,
+                       frame_major, idx_group, following, Bc, Tc, Bf);
     DGMR_CHECK_LAUNCH();
     return 0;
 }
@@ -1847,7 +1868,20 @@ extern "C" int dgmr_frames_s2d_bwd(const float* dout, const int32_t* idx, float*
     const int p = pool ? 2 : 1;
     const int64_t total = (int64_t)B * T * C * H * W;
     hipLaunchKernelGGL(frames_s2d_bwd_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, dout, idx, dframes, B, T, C, H, W, F,
-                       p, frame_major, idx_group);
+                       p, frame_major, idx_group, 0);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_frames_s2d_pair_bwd(const float* dout, const int32_t* idx, float* dfollowing, int N, int Tc, int Tf, int C, int H,
+                                        int W, int F, int pool, int frame_major, int idx_group, void* stream) {
+    if (idx_group < 1) idx_group = N;
+    DGMR_CHECK_ARG(dout && dfollowing, "dgmr_frames_s2d_pair_bwd: null pointer");
+    DGMR_CHECK_ARG(N > 0 && Tc > 0 && Tf > 0, "dgmr_frames_s2d_pair_bwd: N=%d Tc=%d Tf=%d", N, Tc, Tf);
+    const int p = pool ? 2 : 1;
+    const int64_t total = (int64_t)N * Tf * C * H * W;
+    hipLaunchKernelGGL(frames_s2d_bwd_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, dout, idx, dfollowing, N, Tf, C, H, W, F,
+                       p, frame_major, idx_group, Tc);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

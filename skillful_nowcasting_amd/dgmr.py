@@ -6,8 +6,9 @@ OBSERVABLE effect of the reference's step is reproduced — losses, both optimis
 forwards mutate (spectral-norm u/v, BatchNorm running statistics, the CPU RNG stream), including the second
 advance caused by activation checkpointing's recompute and the extra logging forward.
 What is NOT executed is gradient work whose result nothing reads: the D-pass back-propagation into the
-generator (zeroed by ``g_opt.zero_grad()``) and the G-pass weight gradients of the discriminator (zeroed by
-the next ``d_opt.zero_grad()``).  ``strict_reference_semantics=False`` additionally drops the state-only
+generator (zeroed by ``g_opt.zero_grad()``), the G-pass weight gradients of the discriminator (zeroed by
+the next ``d_opt.zero_grad()``) and the G-pass backward through the real half of its discriminator calls (dropped at the
+input: ``Discriminator.forward_split``).  ``strict_reference_semantics=False`` additionally drops the state-only
 forwards (checkpoint recompute, logging forward), so buffers advance fewer times than the reference's.
 """
 import torch
@@ -229,11 +230,18 @@ class DGMR(
         k = predictions.shape[0] // b
         preds = predictions.view(k, b, *predictions.shape[1:])
         grid_cell_reg = self.grid_regularizer.forward_stacked(preds, future_images)
-        real_sequence = torch.cat([images, future_images], dim=1)
-        g_seq = torch.cat([images.unsqueeze(0).expand(k, *images.shape), preds], dim=2)  # [K, B, 4+T, C, H, W]
-        concatenated_inputs = torch.cat([real_sequence.unsqueeze(0).expand(k, *real_sequence.shape).unsqueeze(1), g_seq.unsqueeze(1)],
-                                        dim=1)  # [K, (real, generated), B, ...]
-        concatenated_outputs = self.discriminator(concatenated_inputs.reshape(2 * k * b, *real_sequence.shape[1:]), calls=k)
+        d_frozen = not (torch.is_grad_enabled() and any(p.requires_grad for p in self.discriminator.parameters()))
+        if b % 2 == 0 and d_frozen:  # (training_step freezes the discriminator for this pass; validation runs under no_grad)
+            # the real half of every call only feeds BatchNorm1d's statistics: forward without a graph, no backward, nothing
+            # concatenated or expanded (Discriminator.forward_split; same scores, state and gradients as the joint batch below)
+            concatenated_outputs = self.discriminator.forward_split(images, future_images, preds.reshape(k * b, *predictions.shape[1:]), calls=k)
+        else:  # (an odd batch: the 8x8 maps' two-image tiles need real and generated rows of a call side by side; or a caller who
+            #  wants the discriminator's parameter gradients from this pass)
+            real_sequence = torch.cat([images, future_images], dim=1)
+            g_seq = torch.cat([images.unsqueeze(0).expand(k, *images.shape), preds], dim=2)  # [K, B, 4+T, C, H, W]
+            concatenated_inputs = torch.cat([real_sequence.unsqueeze(0).expand(k, *real_sequence.shape).unsqueeze(1), g_seq.unsqueeze(1)],
+                                            dim=1)  # [K, (real, generated), B, ...]
+            concatenated_outputs = self.discriminator(concatenated_inputs.reshape(2 * k * b, *real_sequence.shape[1:]), calls=k)
         score_generated = concatenated_outputs.view(k, 2, b, *concatenated_outputs.shape[1:])[:, 1]
         generator_disc_loss = loss_hinge_gen(score_generated.reshape(k * b, *concatenated_outputs.shape[1:]))
         generator_loss = ops.axpby(generator_disc_loss, grid_cell_reg, 1.0, self.grid_lambda)

@@ -31,9 +31,10 @@ from ._core import (BNState, CallLayout, SNCall, SPLITK_WS_BYTES, _copy, _dims, 
                     require_weight_layout, set_deterministic, set_grad_touch_hook, sums_buffer, colsum_tmp, to_cl, upload)
 from ._head_ops import (AttentionFn, AxpbyFn, BatchNorm1dFn, GridCellFn, HingeDiscFn, MeanFn, ReluSumHWFn, SNLinear1Fn, adam_update,  # noqa: F401
                         attention, axpby, relu_sum_hw)
-from ._layout_ops import (CatChannelsFn, D2SFramesFn, FramesS2DFn, FramesToBatchFn, PoolAddFn, RepeatBatchFn, StackBatchFn,  # noqa: F401
-                          SumGroupsFn, TimeToChannelsFn, UnstackBatchFn, avg_pool_add, cat_channels, d2s_frames, frames_s2d,
-                          frames_to_batch, repeat_batch, stack_batch, sum_groups, time_to_channels, unstack_batch)
+from ._layout_ops import (CatChannelsFn, D2SFramesFn, FramesS2DFn, FramesS2DPairFn, FramesToBatchFn, InterleaveHalvesFn, PoolAddFn,  # noqa: F401
+                          RepeatBatchFn, StackBatchFn, SumGroupsFn, TimeToChannelsFn, UnstackBatchFn, avg_pool_add, cat_channels,
+                          d2s_frames, frames_s2d, frames_s2d_pair, frames_to_batch, interleave_halves, repeat_batch, stack_batch,
+                          sum_groups, time_to_channels, unstack_batch)
 from ._streams import _on_side_stream, defer_side_join, join_side_streams, side_streams  # noqa: F401
 
 
@@ -167,6 +168,8 @@ class ConvSpec:
     residual_up: bool = False  # the residual is at half resolution and is added with nearest-2x upsampling
     want_stats: bool = False  # also return per-tile partial sums (sum y, sum y^2) of the output: the next BatchNorm's batch statistics
     pool_out: bool = False  # y = AvgPool2d(2) / AvgPool3d(2) of the conv (+ residual at the pooled resolution): DBlock (common.py:233-237)
+    plan_mult: int = 1  # x is one of `plan_mult` equal parts of a batch that other launches cover: forward and data gradient run the kernels
+    #                     the whole batch would get (dgmr_conv_args.plan_n), so every element keeps the summation order it has there
 
     @property
     def groups(self) -> int:
@@ -324,7 +327,7 @@ EPI_PLAIN, EPI_GRU_GATE, EPI_GRU_BLEND, EPI_GRU_GATES2 = 0, 1, 2, 3
 def _launch_conv(x, w_ptr, bias, scale, y, n, d, h, w_, cin, cout, kd, kh, kw, *, upsample=False, pre_relu=False, pre_a=None,
                  pre_b=None, pre_group=1, residual=None, addend=None, mask_src=None, mask_a=None, mask_b=None, mask_group=1,
                  scale_group=None, act_relu=False, w_cin=0, w_coff=0, epi_mode=EPI_PLAIN, gru_h=None, gru_pu=None, pre_out=None,
-                 device=None, w_split=None, residual_up=False, want_stats=False, w_phase=None, pool2=False, gates2=None):
+                 device=None, w_split=None, residual_up=False, want_stats=False, w_phase=None, pool2=False, gates2=None, plan_n=0):
     """`want_stats`: ask for the BatchNorm partial sums of the OUTPUT (dgmr_conv_args.stats_out); returns the [rows, 2, Cout] partials
     tensor, or None when the kernel the library dispatches for these arguments has no fused statistics.
     `pool2`: y is the 2x2 sum pool of the conv (dgmr_conv_args.pool2); returns NotImplemented - nothing launched - when the library has
@@ -332,6 +335,7 @@ def _launch_conv(x, w_ptr, bias, scale, y, n, d, h, w_, cin, cout, kd, kh, kw, *
     `gates2` = (scale2, bias2, addend2, y2, C) with epi_mode EPI_GRU_GATES2: the fused read + update gate launch; returns NotImplemented
     when the library cannot take it."""
     a = ConvArgs()
+    a.plan_n = plan_n if plan_n != n else 0
     if gates2 is not None:
         a.scale2, a.bias2, a.addend2, a.y2, a.gru_split = _p(gates2[0]), _p(gates2[1]), _p(gates2[2]), _p(gates2[3]), int(gates2[4])
     a.w_split = _p(w_split)
@@ -457,6 +461,7 @@ def _conv_data_grad(spec: ConvSpec, geom, x, dy, w, scale, bn_a, bn_b):
     bn = spec.bn
     wt = _flipped_weight(w)
     scale_group = n // spec.groups
+    plan_n = n * spec.plan_mult
     mask = dict(mask_src=x if (bn or spec.pre_relu) else None, **_bn_operands("mask", bn, bn_a, bn_b))
     g_sums = NotImplemented
     if spec.upsample:
@@ -465,14 +470,14 @@ def _conv_data_grad(spec: ConvSpec, geom, x, dy, w, scale, bn_a, bn_b):
         if w_pool is not None:
             g = empty_cl(x.shape, dy)
             g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw, **mask, scale_group=scale_group,
-                                  w_split=_split_planes(w, True), w_phase=w_pool, pool2=True, want_stats=bn is not None)
+                                  w_split=_split_planes(w, True), w_phase=w_pool, pool2=True, want_stats=bn is not None, plan_n=plan_n)
     if g_sums is not NotImplemented:
         pass
     elif spec.upsample:
         g_sums = None
         hi = empty_cl((n, cin, h, wd) if x.dim() == 4 else (n, cin, d, h, wd), dy)
         _launch_conv(dy, _p(wt), None, scale, hi, n, d, h, wd, cout, cin, kd, kh, kw, scale_group=scale_group,
-                     w_split=_split_planes(w, True))
+                     w_split=_split_planes(w, True), plan_n=plan_n)
         g = empty_cl(x.shape, dy)
         call("dgmr_pool_fwd", _p(hi), None, _p(g), n, d, h, wd, cin, 1, 1.0, _p(mask["mask_src"]), _p(bn_a) if bn else None,
              _p(bn_b) if bn else None, bn.group_size if bn else 1, _stream())
@@ -480,7 +485,7 @@ def _conv_data_grad(spec: ConvSpec, geom, x, dy, w, scale, bn_a, bn_b):
         g = empty_cl(x.shape, dy)
         # behind a BatchNorm the epilogue also leaves per-tile (sum g, sum g * x): BatchNorm's backward reduction
         g_sums = _launch_conv(dy, _p(wt), None, scale, g, n, d, h, wd, cout, cin, kd, kh, kw, **mask, scale_group=scale_group,
-                              w_split=_split_planes(w, True), want_stats=bn is not None)
+                              w_split=_split_planes(w, True), want_stats=bn is not None, plan_n=plan_n)
     return g, g_sums
 
 
@@ -561,7 +566,7 @@ class ConvFn(Function):
         partials = _launch_conv(x, _p(w), bias, scale, y, n, d, h, wd, cin, cout, kd, kh, kw, upsample=spec.upsample,
                                 pre_relu=spec.pre_relu, **_bn_operands("pre", spec.bn), residual=residual, act_relu=spec.act_relu,
                                 scale_group=n // groups, w_split=_split_planes(w, False), residual_up=spec.residual_up,
-                                want_stats=spec.want_stats, w_phase=_phase_planes(w) if spec.upsample else None)
+                                want_stats=spec.want_stats, w_phase=_phase_planes(w) if spec.upsample else None, plan_n=n * spec.plan_mult)
         ConvFn._save(ctx, spec, geom, x, w, bias, scale, residual is not None, y if spec.act_relu else None)
         if spec.want_stats:
             if partials is not None:
@@ -599,13 +604,13 @@ class ConvFn(Function):
             sp = empty_cl((n, cout, d, h // 2, wd // 2), x) if is3d else y
             done = _launch_conv(x, _p(w), bias, scale, sp, n, d, h, wd, cin, cout, kd, kh, kw, pre_relu=spec.pre_relu,
                                 residual=None if is3d else residual, scale_group=n // groups, w_split=_split_planes(w, False),
-                                w_phase=w_pool, pool2=True)
+                                w_phase=w_pool, pool2=True, plan_n=n * spec.plan_mult)
             if done is not NotImplemented and is3d:
                 call("dgmr_pool_depth2", _p(sp), _p(residual), _p(y), n, d, (h // 2) * (wd // 2) * cout, _stream())
         if done is NotImplemented:
             full = empty_cl((n, cout, d, h, wd) if is3d else (n, cout, h, wd), x)
             _launch_conv(x, _p(w), bias, scale, full, n, d, h, wd, cin, cout, kd, kh, kw, pre_relu=spec.pre_relu,
-                         scale_group=n // groups, w_split=_split_planes(w, False))
+                         scale_group=n // groups, w_split=_split_planes(w, False), plan_n=n * spec.plan_mult)
             call("dgmr_pool_fwd", _p(full), _p(residual), _p(y), n, d, h, wd, cout, pd, 0.0, None, None, None, 1, _stream())
         ConvFn._save(ctx, spec, geom, x, w, bias, scale, residual is not None, None)
         return y
@@ -631,6 +636,8 @@ class ConvFn(Function):
             dy = dz
         m = n * d * h * wd
         k = kd * kh * kw * cin
+        if (w.requires_grad or (bias is not None and bias.requires_grad)) and spec.plan_mult != 1:
+            raise RuntimeError("conv: a launch on part of a batch (plan_mult) has no weight gradient - its slab order is the whole batch's")
         if w.requires_grad:
             def weight_grad():
                 _conv_weight_grad(spec, geom, x, dy, w, bias, scale, scale_param, bn_a, bn_b, sn_u, sn_v)
