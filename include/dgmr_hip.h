@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DGMR_ABI_VERSION 12
+#define DGMR_ABI_VERSION 13
 
 int dgmr_abi_version(void);
 const char* dgmr_last_error(void);
@@ -508,6 +508,33 @@ typedef struct dgmr_adam_desc {
 } dgmr_adam_desc;
 int dgmr_adam_chunk(void);
 int dgmr_adam_multi(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2, double eps, void* stream);
+
+/* (ABI 13) Gradient guard: the global L2 norm of one optimiser's gradients, torch.nn.utils.clip_grad_norm_'s coefficient and a
+ * "skip this update on NaN / Inf" flag, all formed on the device (no host synchronisation) from ONE extra read of the gradients.
+ * The record lives in device memory; dgmr_grad_norm_multi fills it and dgmr_adam_multi_guarded reads it. */
+typedef struct dgmr_grad_guard {
+    float total_norm;      /* sqrt(sum over tensors of sum g^2): squares and sums in double, rounded to float once */
+    float clip_coef;       /* min(1, max_norm / (total_norm + 1e-6f)) formed in float as torch does (NaN stays NaN); 1 when clipping is off */
+    int32_t skipped;       /* 1 if skip_nonfinite and total_norm is not finite, else 0 */
+    int32_t skipped_total; /* running count: every call adds `skipped` to it (the caller zeroes it once) */
+} dgmr_grad_guard;
+/* Replaces torch.nn.utils.clip_grad_norm_'s norm (torch/nn/utils/clip_grad.py: vector_norm per tensor, vector_norm of the stack,
+ * max_norm / (total_norm + 1e-6) clamped to 1).  descs / n_tensors / total_blocks: the table of the Adam launch(es) of the same step,
+ * over EVERY tensor the norm runs over (block0 ascending from 0); only g, n and block0 are read.  g needs 4-byte alignment only
+ * (views into a flat gradient buffer).  partials (total_blocks doubles) receives one sum of squares per workgroup, tensor_sq
+ * (n_tensors doubles) the per-tensor sums of squares; both are overwritten.  Three launches: per workgroup, per tensor, total.
+ * Deterministic: no atomics and no arrival-order ticket - the association order of every sum depends on the tensor lengths and the
+ * element index only, not on pointer alignment, so separate gradient tensors and views into a flat buffer give the same bits.
+ * The sum of squares (fp32 squares are exact in double and cannot overflow it) is non-finite exactly when a gradient element is:
+ * the pass is also the NaN / Inf detector.  max_norm <= 0: no clipping (clip_coef = 1). */
+int dgmr_grad_norm_multi(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double* partials, double* tensor_sq,
+                         double max_norm, int skip_nonfinite, dgmr_grad_guard* guard, void* stream);
+/* dgmr_adam_multi (torch.optim.Adam as constructed at dgmr/dgmr.py:292-300) on the gradient g * guard->clip_coef (one float product
+ * per element, what clip_grad_norm_'s g.mul_(coef) stores); g itself is not rewritten.  guard->skipped != 0: nothing is stored.
+ * clip_coef == 1 reproduces dgmr_adam_multi bit for bit.  descs may point INTO a larger table (one parameter group's slice of the
+ * table dgmr_grad_norm_multi read): workgroup 0 of the launch is block descs[0].block0; total_blocks counts this slice's only. */
+int dgmr_adam_multi_guarded(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2, double eps,
+                            const dgmr_grad_guard* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /

@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DGMR_LIB=<path>: load another build of the library (A/B runs of a compiler flag or an experimental kernel; the tests use the default)
 LIB_PATH = os.environ.get("DGMR_LIB") or os.path.join(_HERE, "lib", "libdgmr_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 P = c_void_p  # every device pointer and the stream travel as void*
 # deterministic mode (fixed-order cross-workgroup sums: bit-identical runs) is the default; DGMR_DETERMINISTIC=0 switches it off (A/B)
@@ -75,6 +75,22 @@ def _adam_desc_dtype():
 ADAM_DESC_DTYPE = _adam_desc_dtype()  # the same 56 bytes as a numpy record (descriptor tables are filled on the host with numpy)
 assert ADAM_DESC_DTYPE.itemsize == 56
 
+
+class GradGuard(Structure):
+    """Mirror of ``dgmr_grad_guard`` (the record lives on the device; FusedAdam exposes views of its fields)."""
+
+    _fields_ = [("total_norm", c_float), ("clip_coef", c_float), ("skipped", c_int32), ("skipped_total", c_int32)]
+
+
+def _grad_guard_dtype():
+    import numpy as np
+
+    return np.dtype([("total_norm", "<f4"), ("clip_coef", "<f4"), ("skipped", "<i4"), ("skipped_total", "<i4")])
+
+
+GRAD_GUARD_DTYPE = _grad_guard_dtype()
+assert GRAD_GUARD_DTYPE.itemsize == 16 == ctypes.sizeof(GradGuard)
+
 i, f, L = c_int, c_float, c_int64
 # name -> argtypes (every function returns int except the two noted below); must match include/dgmr_hip.h
 SIGNATURES = {
@@ -131,6 +147,8 @@ SIGNATURES = {
     "dgmr_adam": [P, P, P, P, L, c_double, c_double, c_double, c_double, i, P],
     "dgmr_adam_chunk": [],
     "dgmr_adam_multi": [P, i, i, c_double, c_double, c_double, P],
+    "dgmr_grad_norm_multi": [P, i, i, P, P, c_double, i, P, P],
+    "dgmr_adam_multi_guarded": [P, i, i, c_double, c_double, c_double, P, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],

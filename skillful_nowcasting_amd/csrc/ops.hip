@@ -1284,6 +1284,127 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const dgmr_adam_desc* _
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// gradient guard: global L2 norm (torch.nn.utils.clip_grad_norm_), clip coefficient, skip on NaN / Inf
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int adam_desc_of_block(const dgmr_adam_desc* __restrict__ descs, int n_tensors, int b) {
+    int lo = 0, hi = n_tensors - 1;
+    while (lo < hi) {  // last descriptor whose block0 <= b
+        const int mid = (lo + hi + 1) >> 1;
+        if (descs[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Fixed-order sum over a 256-thread workgroup: xor butterfly inside each wave64, then the four wave sums in wave order.
+__device__ __forceinline__ double block_sum_f64(double v, double* smem /* 4 doubles */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((smem[0] + smem[1]) + smem[2]) + smem[3];
+}
+
+// Stage 1, same workgroup -> chunk mapping as adam_multi_kernel.  Thread t owns the four-element groups t, t + 256, t + 512, t + 768 of
+// its chunk and adds their squares in element order, whichever load path brings them in: sixteen-byte loads when the chunk is whole
+// and g is 16-byte aligned, dword loads (bounds-checked, g 4-byte aligned: a view into a flat buffer) otherwise.  Both paths keep all
+// of a lane's loads in flight before the first add.  fp32 -> double is exact and so is the square: one rounding per add.
+__global__ __launch_bounds__(256) void grad_sq_partial_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors,
+                                                              double* __restrict__ partials) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    const dgmr_adam_desc d = descs[adam_desc_of_block(descs, n_tensors, b)];
+    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK;
+    const int64_t left = d.n - i0;  // > 0 by construction of block0
+    const float* __restrict__ g = d.g + i0;
+    float x[ADAM_CHUNK / 256];
+    if (left >= ADAM_CHUNK && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+#pragma unroll
+        for (int k = 0; k < ADAM_CHUNK / 1024; ++k) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(g + k * 1024 + threadIdx.x * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[k * 4 + j] = q[j];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < ADAM_CHUNK / 1024; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = k * 1024 + threadIdx.x * 4 + j;
+                x[k * 4 + j] = e < left ? g[e] : 0.f;  // (+0 leaves a sum of squares unchanged)
+            }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < ADAM_CHUNK / 256; ++k) s += (double)x[k] * (double)x[k];
+    s = block_sum_f64(s, red);
+    if (threadIdx.x == 0) partials[b] = s;
+}
+
+// Stage 2, one workgroup per tensor: thread t adds the tensor's partials t, t + 256, ... in increasing order, then block_sum_f64.
+__global__ __launch_bounds__(256) void grad_sq_tensor_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors, int total_blocks,
+                                                             const double* __restrict__ partials, double* __restrict__ tensor_sq) {
+    __shared__ double red[4];
+    const int t = blockIdx.x;
+    const int b0 = descs[t].block0, b1 = t + 1 < n_tensors ? descs[t + 1].block0 : total_blocks;
+    double s = 0.0;
+    for (int b = b0 + threadIdx.x; b < b1; b += 256) s += partials[b];
+    s = block_sum_f64(s, red);
+    if (threadIdx.x == 0) tensor_sq[t] = s;
+}
+
+// Stage 3, one workgroup: the tensors' sums added one after the other in table order (a few hundred adds; staged through LDS 256 at a
+// time so that the loads are coalesced), then the guard record.  A plain running sum is unchanged by tensors whose gradient is all
+// zero: flat gradient buffers, which give every parameter a (zero) gradient, yield the bits of the run where those have none.
+__global__ __launch_bounds__(256) void grad_guard_finish_kernel(const double* __restrict__ tensor_sq, int n_tensors, float max_norm,
+                                                                int skip_nonfinite, dgmr_grad_guard* __restrict__ guard) {
+    __shared__ double tile[256];
+    double s = 0.0;
+    for (int t0 = 0; t0 < n_tensors; t0 += 256) {
+        tile[threadIdx.x] = t0 + threadIdx.x < n_tensors ? tensor_sq[t0 + threadIdx.x] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0)
+#pragma unroll 16
+            for (int k = 0; k < 256; ++k) s += tile[k];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const float total_norm = (float)sqrt(s);
+    float coef = 1.f;
+    if (max_norm > 0.f) {  // torch: clamp(max_norm / (total_norm + 1e-6), max=1.0) in float; NaN passes through clamp
+        coef = max_norm / (total_norm + 1e-6f);
+        coef = coef > 1.f ? 1.f : coef;
+    }
+    const int skipped = skip_nonfinite && !isfinite(total_norm) ? 1 : 0;
+    guard->total_norm = total_norm;
+    guard->clip_coef = coef;
+    guard->skipped = skipped;
+    guard->skipped_total += skipped;
+}
+
+// adam_multi_kernel on g * clip_coef (the product rounded to float on its own, as clip_grad_norm_'s g.mul_ stores it); nothing is
+// stored when the guard says skip.  `descs` may be one parameter group's slice of a larger table: blocks count from descs[0].block0.
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors, float w1,
+                                                                 float beta2, float w2, float eps,
+                                                                 const dgmr_grad_guard* __restrict__ guard) {
+    if (guard->skipped != 0) return;
+    const float coef = guard->clip_coef;
+    const int b = blockIdx.x + descs[0].block0;
+    const dgmr_adam_desc d = descs[adam_desc_of_block(descs, n_tensors, b)];
+    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK, i1 = i0 + ADAM_CHUNK < d.n ? i0 + ADAM_CHUNK : d.n;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+        const float gi = __fmul_rn(d.g[i], coef), m0 = d.m[i];
+        const float diff = gi - m0;
+        const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);
+        const float vi = fmaf(w2 * gi, gi, beta2 * d.v[i]);
+        d.m[i] = mi;
+        d.v[i] = vi;
+        d.p[i] -= d.step_size * (mi / (sqrtf(vi) / d.bc2_sqrt + eps));
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -2075,6 +2196,31 @@ extern "C" int dgmr_adam_multi(const dgmr_adam_desc* descs, int n_tensors, int t
     DGMR_CHECK_ARG(descs && n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi: bad args");
     hipLaunchKernelGGL(adam_multi_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, (float)(1.0 - beta1), (float)beta2,
                        (float)(1.0 - beta2), (float)eps);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_grad_norm_multi(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double* partials, double* tensor_sq,
+                                    double max_norm, int skip_nonfinite, dgmr_grad_guard* guard, void* stream) {
+    DGMR_CHECK_ARG(descs && partials && tensor_sq && guard, "dgmr_grad_norm_multi: null pointer");
+    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_grad_norm_multi: n_tensors=%d total_blocks=%d must be positive", n_tensors,
+                   total_blocks);
+    DGMR_CHECK_ARG(max_norm == max_norm, "dgmr_grad_norm_multi: max_norm is NaN");
+    hipLaunchKernelGGL(grad_sq_partial_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, partials);
+    hipLaunchKernelGGL(grad_sq_tensor_kernel, dim3(n_tensors), dim3(256), 0, ST, descs, n_tensors, total_blocks, partials, tensor_sq);
+    hipLaunchKernelGGL(grad_guard_finish_kernel, dim3(1), dim3(256), 0, ST, tensor_sq, n_tensors, max_norm > 0.0 ? (float)max_norm : 0.f,
+                       skip_nonfinite, guard);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_adam_multi_guarded(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2,
+                                       double eps, const dgmr_grad_guard* guard, void* stream) {
+    DGMR_CHECK_ARG(descs && guard, "dgmr_adam_multi_guarded: null pointer");
+    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi_guarded: n_tensors=%d total_blocks=%d must be positive", n_tensors,
+                   total_blocks);
+    hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, guard);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

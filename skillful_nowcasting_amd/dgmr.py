@@ -192,6 +192,12 @@ class DGMR(
         import os
 
         self.detect_anomaly = os.environ.get("DGMR_DETECT_ANOMALY", "0") == "1"
+        # Gradient guard (optim.FusedAdam): clip each network's global gradient norm inside its Adam launch and / or skip an update
+        # whose gradients hold NaN / Inf - on the device, no host synchronisation.  Set after construction like detect_anomaly (not
+        # hyper-parameters: hparams and the Hugging Face config stay the reference's); copied onto the optimisers before each step().
+        self.gen_grad_clip_norm = None
+        self.disc_grad_clip_norm = None
+        self.skip_nonfinite_steps = False
 
     def forward(self, x):
         return self.generator(x)
@@ -284,6 +290,7 @@ class DGMR(
                 # AFTER the exchange: every rank scans the same, fully reduced gradients (a scan between begin() and sync() would read
                 # buckets the communication stream is still writing, and a rank that raised alone would leave the others in sync())
                 self._check_finite("the discriminator pass", d_loss_pending, self.discriminator)
+            self._set_guard(d_opt, self.disc_grad_clip_norm)
             d_opt.step()
 
         for _ in range(2):
@@ -338,13 +345,16 @@ class DGMR(
             if self.detect_anomaly:
                 ops.join_side_streams()
                 self._check_finite("the generator pass", [generator_loss, grid_cell_reg], self.generator)
+            self._set_guard(g_opt, self.gen_grad_clip_norm)
             g_opt.step()
             SNScope.weights_changed(self.generator)
         finally:  # an exception (OOM, a refused launch) must not leave the discriminator frozen for a caller that retries
             for p in d_params:
                 p.requires_grad_(True)
-        self.log_dict({"train/d_loss": discriminator_loss, "train/g_loss": generator_loss, "train/grid_loss": grid_cell_reg},
-                      prog_bar=True)
+        metrics = {"train/d_loss": discriminator_loss, "train/g_loss": generator_loss, "train/grid_loss": grid_cell_reg}
+        if self.gen_grad_clip_norm is not None or self.disc_grad_clip_norm is not None or self.skip_nonfinite_steps:
+            metrics.update(self._guard_metrics(g_opt, d_opt))
+        self.log_dict(metrics, prog_bar=True)
         if strict or self.visualize:
             # the logging forward (dgmr.py:213): only its side effects on buffers / RNG matter
             generated_images = self._generate(images, 1, grad=False)
@@ -391,6 +401,27 @@ class DGMR(
         self.grad_sync.broadcast_parameters()
         self.grad_sync.broadcast_buffers()
         return self.grad_sync
+
+    def _set_guard(self, opt, clip_norm):
+        opt = getattr(opt, "optimizer", opt)  # (Lightning hands out wrappers around the optimisers)
+        opt.max_grad_norm = clip_norm
+        opt.skip_nonfinite = bool(self.skip_nonfinite_steps)
+
+    @staticmethod
+    def _guard_metrics(g_opt, d_opt):
+        """Device tensors, no synchronisation; copies, because the optimisers' views are overwritten by the next step.  A network whose
+        guard did not run (no clip norm for it and skip_nonfinite_steps off) has no norm to report."""
+        out = {}
+        skipped = None
+        for key, opt in (("train/g_grad_norm", g_opt), ("train/d_grad_norm", d_opt)):  # (d: the second D update of the step)
+            opt = getattr(opt, "optimizer", opt)
+            if (opt.max_grad_norm is None and not opt.skip_nonfinite) or opt.last_grad_norm is None:
+                continue
+            out[key] = opt.last_grad_norm.clone()
+            skipped = opt.skipped_steps.clone() if skipped is None else skipped + opt.skipped_steps
+        if skipped is not None:
+            out["train/skipped_steps"] = skipped
+        return out
 
     def _check_finite(self, what: str, losses, module):
         """detect_anomaly: raise if a loss or a parameter gradient of `module` holds NaN / Inf (the reference's

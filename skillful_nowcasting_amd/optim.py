@@ -1,4 +1,6 @@
 """Adam through the fused HIP kernel (torch.optim.Adam semantics as used at dgmr/dgmr.py:292-300)."""
+import math
+
 import torch
 
 from . import ops
@@ -9,10 +11,28 @@ class FusedAdam(torch.optim.Optimizer):
 
     State layout (``step``, ``exp_avg``, ``exp_avg_sq``) matches torch.optim.Adam so optimiser checkpoints
     interchange.  Parameters that received no gradient are skipped, like torch does.
+
+    Gradient guard (off by default; with both options at their defaults step() issues exactly the launches it always did):
+
+    * ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_(all parameters of this optimiser, max_grad_norm)`` applied inside the Adam
+      launch - the update uses ``g * clip_coef``, ``p.grad`` itself is never rewritten;
+    * ``skip_nonfinite``: if any gradient element is NaN / Inf, this step stores nothing (``p``, ``exp_avg``, ``exp_avg_sq`` keep their
+      values).  ``state[p]["step"]`` still advances, on the host, for a skipped step: the bias corrections follow ATTEMPTED steps
+      (the step never waits for the device, so the host cannot know; a device-side counter per parameter is not worth it).
+
+    Both are plain attributes (not ``param_groups`` keys: ``state_dict()`` stays interchangeable with torch.optim.Adam) and may be
+    changed between steps.  With either set, step() makes one descriptor table over every parameter with a gradient in ALL groups,
+    one norm pass over it (dgmr_grad_norm_multi: one extra read of the gradients, deterministic, no host synchronisation) and one
+    dgmr_adam_multi_guarded launch per group.  Results stay on the device, as views into the guard's scratch that the next guarded
+    step overwrites: ``last_grad_norm``, ``last_clip_coef``, ``skipped_steps`` (running count), ``last_tensor_grad_norms`` (float64,
+    in the order of ``last_guarded_params``).  ``nonfinite_parameters()`` is the only method that synchronises.
     """
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+        self._guard_active()
 
     flat_grads = None  # set by ddp.GradSync users: gradients then live in one flat buffer that is zeroed, not dropped
 
@@ -22,16 +42,37 @@ class FusedAdam(torch.optim.Optimizer):
             return
         super().zero_grad(set_to_none=set_to_none)
 
-    RING = 4  # pinned descriptor tables in flight (see _step_multi)
+    RING = 4  # pinned descriptor tables in flight (see _upload_table)
     multi_tensor = True  # every tensor of a parameter group in ONE launch (dgmr_adam_multi); False: one dgmr_adam launch per tensor
+    skip_nonfinite = False  # (class default: an optimiser restored by pickle has the guard off)
+
+    @property
+    def max_grad_norm(self):
+        return self.__dict__.get("_max_grad_norm")
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            value = float(value)
+            if not (math.isfinite(value) and value > 0.0):
+                raise ValueError(f"max_grad_norm must be None or a finite float > 0, got {value}")
+        self.__dict__["_max_grad_norm"] = value
+
+    def _guard_active(self) -> bool:
+        on = self.max_grad_norm is not None or bool(self.skip_nonfinite)
+        if on and not self.multi_tensor:
+            raise ValueError("the gradient guard (max_grad_norm / skip_nonfinite) needs multi_tensor = True")
+        return on
 
     @torch.no_grad()
     def step(self, closure=None):
+        guarded = self._guard_active()
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         written = []
+        rows, slices = [], []  # guarded: one table over all groups, (first row, rows, b1, b2, eps) per group
         for group in self.param_groups:
             b1, b2 = group["betas"]
             todo = []
@@ -50,20 +91,23 @@ class FusedAdam(torch.optim.Optimizer):
                 if g.stride() != p.stride():  # kernels index raw storage: bring the gradient to the parameter's layout
                     g = torch.empty_like(p).copy_(g)
                 if self.multi_tensor:
-                    todo.append((p, g, st))
+                    todo.append((p, g, st, group["lr"], b1, b2))
                 else:
                     ops.adam_update(p, g, st["exp_avg"], st["exp_avg_sq"], st["step"], group["lr"], b1, b2, group["eps"])
-            if todo:
-                self._step_multi(todo, group["lr"], b1, b2, group["eps"])
+            if todo and guarded:
+                slices.append((len(rows), len(todo), b1, b2, group["eps"]))
+                rows += todo
+            elif todo:
+                self._step_multi(todo, b1, b2, group["eps"])
+        if rows:
+            self._step_guarded(rows, slices)
         ops._core.note_optimizer_step(written)  # (the images of THESE weights are stale; everything else keeps its caches)
         return loss
 
-    def _step_multi(self, todo, lr, b1, b2, eps):
+    def _upload_table(self, rows):
         """One descriptor per tensor (pointers, length, first workgroup, the two step-dependent scalars - torch keeps a step counter per
-        parameter), uploaded as one pinned-memory copy, then ONE launch.  The scalars are formed in double and rounded once, like
-        dgmr_adam does."""
-        import math
-
+        parameter), uploaded as one pinned-memory copy.  The scalars are formed in double and rounded once, like dgmr_adam does.
+        -> (device table, first workgroup of every row + the total)"""
         import numpy as np
 
         from ._lib import ADAM_DESC_DTYPE, load
@@ -71,7 +115,7 @@ class FusedAdam(torch.optim.Optimizer):
         chunk = self.__dict__.get("_chunk")
         if chunk is None:
             chunk = self.__dict__["_chunk"] = int(load().dgmr_adam_chunk())
-        n = len(todo)
+        n = len(rows)
         # The upload is asynchronous and the step never synchronises the host: a pinned table must not be rewritten before the copy
         # that reads it has executed (two step() calls per training step, several parameter groups per call).  A ring of pinned
         # tables, each with the event of its last copy; a slot is reused only after that event.
@@ -86,18 +130,96 @@ class FusedAdam(torch.optim.Optimizer):
             if ent is not None:
                 ent[2].synchronize()
             ent = ring[slot] = (torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
-                                torch.empty(nbytes, dtype=torch.uint8, device=todo[0][0].device), torch.cuda.Event())
+                                torch.empty(nbytes, dtype=torch.uint8, device=rows[0][0].device), torch.cuda.Event())
         else:
             ent[2].synchronize()  # (long done in practice: RING - 1 other uploads lie in between)
         host, dev, done = ent
         tab = np.frombuffer(host.numpy(), dtype=ADAM_DESC_DTYPE, count=n)
         block = 0
-        for i, (p, g, st) in enumerate(todo):
+        block0 = []
+        for i, (p, g, st, lr, b1, b2) in enumerate(rows):
             numel = p.numel()
             step = st["step"]
             tab[i] = (p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), numel, block,
                       np.float32(lr / (1.0 - b1 ** step)), np.float32(math.sqrt(1.0 - b2 ** step)), 0)
+            block0.append(block)
             block += (numel + chunk - 1) // chunk
+        block0.append(block)
         dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
         done.record()
-        ops.call("dgmr_adam_multi", dev.data_ptr(), n, block, float(b1), float(b2), float(eps), ops._stream())
+        return dev, block0
+
+    def _step_multi(self, todo, b1, b2, eps):
+        """The tensors of one parameter group: one table upload, then ONE launch."""
+        dev, block0 = self._upload_table(todo)
+        ops.call("dgmr_adam_multi", dev.data_ptr(), len(todo), block0[-1], float(b1), float(b2), float(eps), ops._stream())
+
+    # ------------------------------------------------------------------------------------------
+    # gradient guard
+    # ------------------------------------------------------------------------------------------
+    def _step_guarded(self, rows, slices):
+        """One table over all groups (one upload), the norm pass over all of it, then the guarded Adam launch on every group's slice."""
+        from ._lib import ADAM_DESC_DTYPE
+
+        dev, block0 = self._upload_table(rows)
+        n, blocks = len(rows), block0[-1]
+        device = rows[0][0].device
+        d = self.__dict__
+        if d.get("_guard") is None:  # 16 bytes, dgmr_grad_guard; allocated once (skipped_total lives in it)
+            d["_guard"] = torch.zeros(4, dtype=torch.int32, device=device)
+        if d.get("_partials") is None or d["_partials"].numel() < blocks:
+            d["_partials"] = torch.empty(blocks, dtype=torch.float64, device=device)
+        if d.get("_tensor_sq") is None or d["_tensor_sq"].numel() < n:
+            d["_tensor_sq"] = torch.empty(n, dtype=torch.float64, device=device)
+        guard = d["_guard"]
+        stream = ops._stream()
+        ops.call("dgmr_grad_norm_multi", dev.data_ptr(), n, blocks, d["_partials"].data_ptr(), d["_tensor_sq"].data_ptr(),
+                 float(self.max_grad_norm or 0.0), int(bool(self.skip_nonfinite)), guard.data_ptr(), stream)
+        for first, count, b1, b2, eps in slices:
+            ops.call("dgmr_adam_multi_guarded", dev.data_ptr() + first * ADAM_DESC_DTYPE.itemsize, count,
+                     block0[first + count] - block0[first], float(b1), float(b2), float(eps), guard.data_ptr(), stream)
+        d["_guarded_params"] = [r[0] for r in rows]
+
+    @property
+    def last_grad_norm(self):
+        """Global L2 norm of the gradients of the last guarded step: 0-d float32 device tensor, a view (None before the first)."""
+        g = self.__dict__.get("_guard")
+        return None if g is None else g[:2].view(torch.float32)[0]
+
+    @property
+    def last_clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)) of the last guarded step (1 without max_grad_norm): 0-d float32 device view."""
+        g = self.__dict__.get("_guard")
+        return None if g is None else g[:2].view(torch.float32)[1]
+
+    @property
+    def skipped_steps(self):
+        """How many guarded steps were skipped so far: 0-d int32 device view."""
+        g = self.__dict__.get("_guard")
+        return None if g is None else g[3]
+
+    @property
+    def last_guarded_params(self):
+        """The parameters the last guarded step ran over (those with a gradient), in table order."""
+        return list(self.__dict__.get("_guarded_params", ()))
+
+    @property
+    def last_tensor_grad_norms(self):
+        """Per-tensor L2 norms of the last guarded step in the order of last_guarded_params: float64 device tensor, the square root
+        of a view into the scratch (no synchronisation)."""
+        sq = self.__dict__.get("_tensor_sq")
+        return None if sq is None else sq[:len(self.__dict__["_guarded_params"])].sqrt()
+
+    def nonfinite_parameters(self, names=None):
+        """The parameters of the last guarded step whose gradient held NaN / Inf (their per-tensor norm is not finite).  SYNCHRONISES
+        the host.  names: optional (name, parameter) pairs, e.g. ``module.named_parameters()`` - the offenders' names are returned
+        instead of the parameters."""
+        norms = self.last_tensor_grad_norms
+        if norms is None:
+            return []
+        bad = (~torch.isfinite(norms)).nonzero().flatten().tolist()
+        params = [self.__dict__["_guarded_params"][i] for i in bad]
+        if names is None:
+            return params
+        by_id = {id(p): name for name, p in names}
+        return [by_id.get(id(p), "?") for p in params]
