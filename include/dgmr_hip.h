@@ -536,6 +536,22 @@ int dgmr_grad_norm_multi(const dgmr_adam_desc* descs, int n_tensors, int total_b
 int dgmr_adam_multi_guarded(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2, double eps,
                             const dgmr_grad_guard* guard, void* stream);
 
+/* (added under ABI 13: new symbols only) Exponential moving average of the weights inside the Adam launch.  Stands for
+ * torch.optim.swa_utils.get_ema_multi_avg_fn(decay), i.e. Tensor.lerp_(param, 1 - decay) on every shadow after the optimiser step:
+ * e = w < 0.5f ? fmaf(w, p_new - e, e) : p_new - (p_new - e) * (1.f - w) (at::lerp), with p_new the float this launch has just stored
+ * to p and w = (float)ema_weight = 1 - decay, formed in double by the caller and rounded once here.  ema: device array of n_tensors
+ * pointers parallel to descs (a shadow has its parameter's length and element order); a NULL entry leaves that tensor without an
+ * average.  guard == NULL: p, m, v come out as from dgmr_adam_multi; otherwise as from dgmr_adam_multi_guarded (g * clip_coef; a
+ * skipped step stores nothing, to the shadows either) - bit for bit in both cases.  descs / ema may be the matching slices of larger
+ * tables, as for dgmr_adam_multi_guarded.  ema_weight outside [0, 1] (or NaN) is refused. */
+int dgmr_adam_multi_ema(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, double beta1, double beta2,
+                        double eps, double ema_weight, const dgmr_grad_guard* guard, void* stream);
+/* The evaluation swap: exchanges the contents of descs[i].p and ema[i] for every i in one launch (what evaluating
+ * swa_utils.AveragedModel.module instead of the model does, in place: the parameters keep their addresses).  Reads only p, n and
+ * block0 of each descriptor; NULL entries of ema are skipped.  Twice is the identity.  The caller invalidates whatever it caches
+ * from the parameters. */
+int dgmr_swap_multi(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed

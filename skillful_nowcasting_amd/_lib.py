@@ -149,6 +149,8 @@ SIGNATURES = {
     "dgmr_adam_multi": [P, i, i, c_double, c_double, c_double, P],
     "dgmr_grad_norm_multi": [P, i, i, P, P, c_double, i, P, P],
     "dgmr_adam_multi_guarded": [P, i, i, c_double, c_double, c_double, P, P],
+    "dgmr_adam_multi_ema": [P, P, i, i, c_double, c_double, c_double, c_double, P, P],
+    "dgmr_swap_multi": [P, P, i, i, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],

@@ -1405,6 +1405,142 @@ __global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const dgmr_adam
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// weight EMA (torch.optim.swa_utils.get_ema_multi_avg_fn: ema.lerp_(param, 1 - decay)) inside the Adam launch, and the evaluation swap
+// ------------------------------------------------------------------------------------------------
+// One element of adam_multi_kernel (GUARDED: of adam_multi_guarded_kernel), the same expressions in the same order, followed by
+// Tensor.lerp_ of the shadow towards the float just formed for p (at::lerp's two branches).  e is touched only when has_e.
+template <bool GUARDED>
+__device__ __forceinline__ void adam_ema_element(float g, float coef, float& m, float& v, float& p, float& e, bool has_e, float w1,
+                                                 float beta2, float w2, float eps, float step_size, float bc2_sqrt, float we) {
+    const float gi = GUARDED ? __fmul_rn(g, coef) : g, m0 = m;
+    const float diff = gi - m0;
+    const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);
+    const float vi = fmaf(w2 * gi, gi, beta2 * v);
+    m = mi;
+    v = vi;
+    p -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+    if (has_e) {
+        const float pn = p, e0 = e;
+        e = we < 0.5f ? fmaf(we, pn - e0, e0) : pn - (pn - e0) * (1.f - we);
+    }
+}
+
+// adam_multi_kernel / adam_multi_guarded_kernel plus the shadow update in the same pass: 36 bytes per element instead of 28, no second
+// launch and no second read of p.  Same workgroup -> chunk mapping; `descs` (and `ema`, its parallel array of shadow pointers, NULL =
+// no shadow) may be a group's slice of a larger table.  A whole chunk whose p / m / v / shadow pointers are 16-byte aligned moves as
+// f32x4: lane t owns elements 4t .. 4t + 3 of each 1024-element quarter and has the loads of all four quarters in flight before the
+// first store.  g is read the same way when it is aligned and dword by dword when it is a 4-byte aligned view into a flat gradient
+// buffer.  Everything else (a tensor's last chunk, short tensors) takes the bounds-checked dword loop of adam_multi_kernel.
+template <bool GUARDED>
+__global__ __launch_bounds__(256) void adam_multi_ema_kernel(const dgmr_adam_desc* __restrict__ descs, float* const* __restrict__ ema,
+                                                             int n_tensors, float w1, float beta2, float w2, float eps, float we,
+                                                             const dgmr_grad_guard* __restrict__ guard) {
+    float coef = 1.f;
+    if (GUARDED) {
+        if (guard->skipped != 0) return;
+        coef = guard->clip_coef;
+    }
+    const int b = blockIdx.x + descs[0].block0;
+    const int t = adam_desc_of_block(descs, n_tensors, b);
+    const dgmr_adam_desc d = descs[t];
+    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK;
+    const int64_t left = d.n - i0;  // > 0 by construction of block0
+    const bool has_e = ema[t] != nullptr;
+    float* __restrict__ p = d.p + i0;
+    float* __restrict__ m = d.m + i0;
+    float* __restrict__ v = d.v + i0;
+    float* __restrict__ e = has_e ? ema[t] + i0 : nullptr;
+    const float* __restrict__ g = d.g + i0;
+    constexpr int Q = ADAM_CHUNK / 1024;
+    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                            reinterpret_cast<uintptr_t>(e);
+    if (left >= ADAM_CHUNK && (align & 15) == 0) {
+        f32x4 gq[Q], mq[Q], vq[Q], pq[Q], eq[Q];
+        const int lane = threadIdx.x * 4;
+        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+#pragma unroll
+            for (int k = 0; k < Q; ++k) gq[k] = *reinterpret_cast<const f32x4*>(g + k * 1024 + lane);
+        } else {
+#pragma unroll
+            for (int k = 0; k < Q; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gq[k][j] = g[k * 1024 + lane + j];
+        }
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            mq[k] = *reinterpret_cast<const f32x4*>(m + k * 1024 + lane);
+            vq[k] = *reinterpret_cast<const f32x4*>(v + k * 1024 + lane);
+            pq[k] = *reinterpret_cast<const f32x4*>(p + k * 1024 + lane);
+        }
+        if (has_e) {
+#pragma unroll
+            for (int k = 0; k < Q; ++k) eq[k] = *reinterpret_cast<const f32x4*>(e + k * 1024 + lane);
+        }
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float mj = mq[k][j], vj = vq[k][j], pj = pq[k][j], ej = has_e ? eq[k][j] : 0.f;
+                adam_ema_element<GUARDED>(gq[k][j], coef, mj, vj, pj, ej, has_e, w1, beta2, w2, eps, d.step_size, d.bc2_sqrt, we);
+                mq[k][j] = mj;
+                vq[k][j] = vj;
+                pq[k][j] = pj;
+                eq[k][j] = ej;
+            }
+            *reinterpret_cast<f32x4*>(m + k * 1024 + lane) = mq[k];
+            *reinterpret_cast<f32x4*>(v + k * 1024 + lane) = vq[k];
+            *reinterpret_cast<f32x4*>(p + k * 1024 + lane) = pq[k];
+            if (has_e) *reinterpret_cast<f32x4*>(e + k * 1024 + lane) = eq[k];
+        }
+        return;
+    }
+    const int n = left < ADAM_CHUNK ? (int)left : ADAM_CHUNK;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        float mj = m[i], vj = v[i], pj = p[i], ej = has_e ? e[i] : 0.f;
+        adam_ema_element<GUARDED>(g[i], coef, mj, vj, pj, ej, has_e, w1, beta2, w2, eps, d.step_size, d.bc2_sqrt, we);
+        m[i] = mj;
+        v[i] = vj;
+        p[i] = pj;
+        if (has_e) e[i] = ej;
+    }
+}
+
+// p <-> shadow, every tensor in one launch (the evaluation swap: what swa_utils users do with AveragedModel.module, in place here
+// because the modules' caches are keyed on the parameters' addresses).  Reads p, n and block0 of the descriptor only.
+__global__ __launch_bounds__(256) void swap_multi_kernel(const dgmr_adam_desc* __restrict__ descs, float* const* __restrict__ ema,
+                                                         int n_tensors) {
+    const int b = blockIdx.x + descs[0].block0;
+    const int t = adam_desc_of_block(descs, n_tensors, b);
+    if (ema[t] == nullptr) return;
+    const int64_t i0 = (int64_t)(b - descs[t].block0) * ADAM_CHUNK;
+    const int64_t left = descs[t].n - i0;
+    float* __restrict__ p = descs[t].p + i0;
+    float* __restrict__ e = ema[t] + i0;
+    constexpr int Q = ADAM_CHUNK / 1024;
+    if (left >= ADAM_CHUNK && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(e)) & 15) == 0) {
+        f32x4 pq[Q], eq[Q];
+        const int lane = threadIdx.x * 4;
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            pq[k] = *reinterpret_cast<const f32x4*>(p + k * 1024 + lane);
+            eq[k] = *reinterpret_cast<const f32x4*>(e + k * 1024 + lane);
+        }
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            *reinterpret_cast<f32x4*>(p + k * 1024 + lane) = eq[k];
+            *reinterpret_cast<f32x4*>(e + k * 1024 + lane) = pq[k];
+        }
+        return;
+    }
+    const int n = left < ADAM_CHUNK ? (int)left : ADAM_CHUNK;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float pi = p[i], ei = e[i];
+        p[i] = ei;
+        e[i] = pi;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -2221,6 +2357,31 @@ extern "C" int dgmr_adam_multi_guarded(const dgmr_adam_desc* descs, int n_tensor
                    total_blocks);
     hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), (float)eps, guard);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_adam_multi_ema(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, double beta1,
+                                   double beta2, double eps, double ema_weight, const dgmr_grad_guard* guard, void* stream) {
+    DGMR_CHECK_ARG(descs && ema, "dgmr_adam_multi_ema: null pointer");
+    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi_ema: n_tensors=%d total_blocks=%d must be positive", n_tensors,
+                   total_blocks);
+    DGMR_CHECK_ARG(ema_weight >= 0.0 && ema_weight <= 1.0, "dgmr_adam_multi_ema: ema_weight=%g out of [0, 1]", ema_weight);  // (NaN too)
+    if (guard)
+        hipLaunchKernelGGL(adam_multi_ema_kernel<true>, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors, (float)(1.0 - beta1),
+                           (float)beta2, (float)(1.0 - beta2), (float)eps, (float)ema_weight, guard);
+    else
+        hipLaunchKernelGGL(adam_multi_ema_kernel<false>, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)ema_weight, guard);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_swap_multi(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, void* stream) {
+    DGMR_CHECK_ARG(descs && ema, "dgmr_swap_multi: null pointer");
+    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_swap_multi: n_tensors=%d total_blocks=%d must be positive", n_tensors,
+                   total_blocks);
+    hipLaunchKernelGGL(swap_multi_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

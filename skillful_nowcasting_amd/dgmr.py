@@ -88,6 +88,8 @@ except Exception:  # pragma: no cover - depends on the environment
             hp.update(overrides)
             model = cls(**hp)
             model.load_state_dict(ckpt["state_dict"], strict=strict)
+            if "generator_ema" in ckpt:  # (DGMR.on_save_checkpoint; kept on the host until the model is on its device)
+                model.load_ema_state_dict(ckpt["generator_ema"])
             return model
 
 
@@ -198,6 +200,11 @@ class DGMR(
         self.gen_grad_clip_norm = None
         self.disc_grad_clip_norm = None
         self.skip_nonfinite_steps = False
+        # Generator weight EMA (optim.FusedAdam: the average is updated inside the generator's Adam launch).  Set after construction
+        # like the guard; the discriminator is never averaged.  `with model.ema_scope():` evaluates the averaged generator.
+        self.gen_ema_decay = None
+        self.gen_ema_warmup = False
+        self._in_ema_scope = False
 
     def forward(self, x):
         return self.generator(x)
@@ -257,6 +264,9 @@ class DGMR(
         """One GAN step (dgmr/dgmr.py:137-218)."""
         from .nn import SNScope
 
+        if self._in_ema_scope:
+            raise RuntimeError("training_step inside ema_scope(): the generator holds its averaged weights, Adam would update the "
+                               "average as if it were the weights")
         # (the generator's spectral-norm sequences of one step repeat from step to step: each is issued one forward ahead, nn.SNScope)
         with SNScope.step(self.generator):
             return self._training_step(batch, batch_idx)
@@ -346,6 +356,7 @@ class DGMR(
                 ops.join_side_streams()
                 self._check_finite("the generator pass", [generator_loss, grid_cell_reg], self.generator)
             self._set_guard(g_opt, self.gen_grad_clip_norm)
+            self._set_ema(g_opt)
             g_opt.step()
             SNScope.weights_changed(self.generator)
         finally:  # an exception (OOM, a refused launch) must not leave the discriminator frozen for a caller that retries
@@ -381,10 +392,14 @@ class DGMR(
             self.visualize_step(images, future_images, generated_images, self.global_iteration, step="val")
         return {"d_loss": discriminator_loss.detach(), "g_loss": generator_loss.detach(), "grid_loss": grid_cell_reg.detach()}
 
-    def sample(self, images, num_samples: int = None):
+    def sample(self, images, num_samples: int = None, use_ema: bool = False):
         """Ensemble nowcast: `num_samples` forecasts per input sequence -> [num_samples, B, T, C, H, W] (the reference's usage is a
         Python loop of `model(x)` calls, README.md:73-91; here the context stack runs once and the sampler on all draws at once).
-        Call under model.eval() for inference; in train mode it is `num_samples` consecutive train-mode forwards."""
+        Call under model.eval() for inference; in train mode it is `num_samples` consecutive train-mode forwards.
+        use_ema: draw from the averaged generator (the call runs inside ema_scope())."""
+        if use_ema:
+            with self.ema_scope():
+                return self.sample(images, num_samples)
         k = self.num_samples if num_samples is None else num_samples
         out = self._generate(images.float(), k, grad=False)
         return out.view(k, images.shape[0], *out.shape[1:])
@@ -401,6 +416,108 @@ class DGMR(
         self.grad_sync.broadcast_parameters()
         self.grad_sync.broadcast_buffers()
         return self.grad_sync
+
+    # ------------------------------------------------------------------------------------------
+    # generator weight EMA
+    # ------------------------------------------------------------------------------------------
+    def _gen_optimizer(self, required: bool = True):
+        """The generator's FusedAdam.  An EMA state that a checkpoint brought before the optimisers existed (on_load_checkpoint) is
+        handed over here, so every reader of the average - ema_scope, sample(use_ema=True), ema_state_dict, on_save_checkpoint,
+        training_step - sees it.  required=False: None where there are no optimisers yet."""
+        try:
+            opt = self.optimizers()[0]
+        except (RuntimeError, IndexError, TypeError, AttributeError):  # (Lightning: not attached to a Trainer, or none set up yet)
+            if required:
+                raise
+            return None
+        opt = getattr(opt, "optimizer", opt)  # (Lightning hands out wrappers around the optimisers)
+        pending = self.__dict__.pop("_gen_ema_pending", None)
+        if pending is not None:
+            self._load_ema_into(opt, pending)
+        return opt
+
+    def _set_ema(self, opt):
+        self._gen_optimizer()  # (a checkpoint's EMA state that was still waiting is handed over before the step)
+        opt = getattr(opt, "optimizer", opt)
+        opt.ema_decay = self.gen_ema_decay
+        opt.ema_warmup = bool(self.gen_ema_warmup)
+
+    def ema_scope(self):
+        """`with model.ema_scope():` - the generator's parameters hold their moving averages inside the block and the live weights
+        again after it (FusedAdam.swap_ema on entry and on exit: one launch each, and only the swapped weights' cached images are
+        rebuilt).  Everything that reads the parameters sees the average: forward, sample, validation_step, state_dict(),
+        save_pretrained.  Buffers (spectral-norm u / v, BatchNorm running statistics) are not averaged: the live ones are used.
+        Not re-entrant, and training_step refuses to run inside it."""
+        import contextlib
+
+        from .nn import SNScope
+
+        @contextlib.contextmanager
+        def scope():
+            if self._in_ema_scope:
+                raise RuntimeError("ema_scope() is already active: a second swap would put the live weights back")
+            opt = self._gen_optimizer()
+            opt.swap_ema()
+            SNScope.weights_changed(self.generator)
+            self._in_ema_scope = True
+            try:
+                yield self
+            finally:
+                self._in_ema_scope = False
+                opt.swap_ema()
+                SNScope.weights_changed(self.generator)
+
+        return scope()
+
+    def ema_state_dict(self):
+        """The generator's averaged weights by parameter name (`self.generator.named_parameters()`), contiguous like state_dict()'s,
+        plus "num_updates".  Parameters that were never stepped with EMA on have no entry: their average is the parameter."""
+        if self._in_ema_scope:
+            raise RuntimeError("ema_state_dict() inside ema_scope(): the shadows hold the live weights there; use state_dict()")
+        opt = self._gen_optimizer()
+        out = {"num_updates": int(opt.ema_num_updates)}
+        for name, p in self.generator.named_parameters():
+            e = opt.ema(p)
+            if e is not None:
+                out[name] = e.detach().clone(memory_format=torch.contiguous_format)
+        return out
+
+    def load_ema_state_dict(self, state):
+        """What ema_state_dict() returned.  May be called before the model is moved to its device: the optimiser keeps the tensors on
+        the host until the parameters are first used there."""
+        if self._in_ema_scope:
+            raise RuntimeError("load_ema_state_dict() inside ema_scope()")
+        self._load_ema_into(self._gen_optimizer(), state)
+
+    def _load_ema_into(self, opt, state):
+        index = opt._param_index()
+        params = dict(self.generator.named_parameters())
+        unknown = [k for k in state if k != "num_updates" and k not in params]
+        if unknown:
+            raise KeyError(f"generator EMA state names unknown parameters: {unknown[:5]}")
+        opt.load_ema_state_dict({"num_updates": state.get("num_updates", 0),
+                                 "shadows": {index[params[k]]: t for k, t in state.items() if k != "num_updates"}})
+
+    def on_save_checkpoint(self, checkpoint):
+        """Lightning hook: the averaged generator travels under checkpoint["generator_ema"] when EMA is on."""
+        if self.gen_ema_decay is None:
+            return
+        if self._gen_optimizer(required=False) is None and "_gen_ema_pending" in self.__dict__:
+            checkpoint["generator_ema"] = self._gen_ema_pending  # (loaded, never handed over: it goes out as it came in)
+        else:
+            checkpoint["generator_ema"] = self.ema_state_dict()
+
+    def on_load_checkpoint(self, checkpoint):
+        """Lightning restores the module before the Trainer has set the optimisers up: the state then waits in _gen_ema_pending
+        until _gen_optimizer() first finds the generator's optimiser."""
+        if "generator_ema" not in checkpoint:
+            return
+        if self._in_ema_scope:
+            raise RuntimeError("on_load_checkpoint() inside ema_scope()")
+        if self._gen_optimizer(required=False) is None:
+            self._gen_ema_pending = checkpoint["generator_ema"]
+        else:
+            self.load_ema_state_dict(checkpoint["generator_ema"])
 
     def _set_guard(self, opt, clip_norm):
         opt = getattr(opt, "optimizer", opt)  # (Lightning hands out wrappers around the optimisers)
