@@ -553,6 +553,32 @@ int dgmr_adam_multi_ema(const dgmr_adam_desc* descs, float* const* ema, int n_te
 int dgmr_swap_multi(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Importance-sampled training crops from full frames (data.py: ImportanceCropLoader).  New symbols, same ABI version.
+ * Both entry points read `frames` as ONE sequence [T][H][W][C], channels last as rows arrive, in its storage dtype; only element
+ * alignment of `frames` is assumed.  The physical value of an element is x = fadd_rn(fmul_rn((float)raw, scale), offset): two
+ * separately rounded fp32 operations, never an fma (torch's raw.float() * scale + offset, bit for bit).  An element is MISSING when
+ * !(x >= 0.f): negative, -inf or NaN.  Argument errors (unknown dtype, crop % cell != 0, H < crop, W < crop, non-positive extents or
+ * sat_scale, null pointers) return < 0 and set dgmr_last_error() before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define DGMR_DT_U8 0
+#define DGMR_DT_I16 1
+#define DGMR_DT_F16 2
+#define DGMR_DT_F32 3
+/* scores[gy][gx] = sum over t, c and the crop x crop pixels with top-left (gy*cell, gx*cell) of  -expm1(-(double)x / sat_scale)
+ * (missing elements contribute 0);  missing[gy][gx] = number of missing elements in the same box.
+ * Gy = (H - crop)/cell + 1, Gx = (W - crop)/cell + 1; crop % cell == 0; H, W >= crop; a remainder of H or W beyond the last full cell is
+ * never covered.  cell_sums [H/cell][W/cell] doubles and cell_missing [H/cell][W/cell] int32: caller's workspace, overwritten.
+ * Terms and sums are doubles added in an order that depends on indices only: two launches give the same bits, and a host evaluation
+ * of the same formula agrees to summation order (~1e-13), so that an accept decision u < q falls the same way on both. */
+int dgmr_crop_scores(const void* frames, int dtype, int T, int H, int W, int C, float scale, float offset, double sat_scale,
+                     int cell, int crop, double* cell_sums, int32_t* cell_missing, double* scores, int32_t* missing, void* stream);
+/* out[n][t][c][i][j] = x(frames[t][y_n + i][x_n + j][c]) for the N origins (y_n, x_n) in `origins` (device, [N][2] int32), fp32, the
+ * model's layout.  clamp_missing != 0: missing elements are written as missing_fill.  N == 0: no launch, returns 0.  Every load is
+ * guarded: an element outside the frame (an origin outside [0, H - crop] x [0, W - crop]) is written as missing_fill. */
+int dgmr_crop_gather(const void* frames, int dtype, int T, int H, int W, int C, const int32_t* origins, int N, int crop,
+                     float scale, float offset, int clamp_missing, float missing_fill, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

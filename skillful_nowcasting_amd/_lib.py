@@ -151,6 +151,8 @@ SIGNATURES = {
     "dgmr_adam_multi_guarded": [P, i, i, c_double, c_double, c_double, P, P],
     "dgmr_adam_multi_ema": [P, P, i, i, c_double, c_double, c_double, c_double, P, P],
     "dgmr_swap_multi": [P, P, i, i, P],
+    "dgmr_crop_scores": [P, i, i, i, i, i, f, f, c_double, i, i, P, P, P, P, P],
+    "dgmr_crop_gather": [P, i, i, i, i, i, P, i, i, f, f, i, f, P, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],
