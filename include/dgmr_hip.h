@@ -494,7 +494,9 @@ int dgmr_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr
 /* (ABI 9) All tensors of one optimiser (dgmr/dgmr.py:292-300: one Adam per network) in ONE launch.  descs: device array, one entry per
  * tensor in ascending block0 order; block0 = first workgroup of the tensor when every tensor gets ceil(n / dgmr_adam_chunk())
  * workgroups; step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) rounded from double by the caller, as dgmr_adam
- * forms them (torch keeps one step counter per parameter: they travel per tensor).  Same arithmetic per element as dgmr_adam. */
+ * forms them (torch keeps one step counter per parameter: they travel per tensor).  Same arithmetic per element as dgmr_adam.
+ * descs may point INTO a larger table (one parameter group's slice), as for dgmr_adam_multi_guarded: workgroup 0 of the launch is
+ * block descs[0].block0; total_blocks counts this slice's only. */
 typedef struct dgmr_adam_desc {
     float* p;
     const float* g;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "../../include/dgmr_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -30,6 +32,13 @@ extern int g_deterministic;  // dgmr_set_deterministic (ops.hip): fixed-order cr
     } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Element-wise launches (ops.hip, optim.hip): 256 threads, a capped grid that strides over the items; `stream` is the entry point's argument.
+constexpr int EW_THREADS = 256;
+static inline int ew_blocks(int64_t n_items) { return (int)std::min<int64_t>((n_items + EW_THREADS - 1) / EW_THREADS, 256 * 16); }
+#define GRID_STRIDE(i, n) \
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+#define ST ((hipStream_t)stream)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

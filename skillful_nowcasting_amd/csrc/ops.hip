@@ -1,6 +1,6 @@
 // HBM-bound kernels of the DGMR step for gfx950: spectral-norm power iteration, BatchNorm statistics and
-// backward, pooling / space-to-depth layout moves, ConvGRU gating, latent attention, discriminator heads,
-// losses and Adam.  All of them are bandwidth- or latency-bound (no MFMA): coalesced, 16-byte vectorised
+// backward, pooling / space-to-depth layout moves, ConvGRU gating, latent attention, discriminator heads
+// and losses (the optimiser: optim.hip).  All of them are bandwidth- or latency-bound (no MFMA): coalesced, 16-byte vectorised
 // where the layout allows, per-channel reductions accumulate in double so that E[x^2]-E[x]^2 stays accurate.
 #include <stdarg.h>
 
@@ -30,12 +30,7 @@ extern "C" int dgmr_get_deterministic(void) { return g_deterministic; }
 
 namespace {
 
-constexpr int EW_THREADS = 256;
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-inline int ew_blocks(int64_t n_items) { return (int)std::min<int64_t>((n_items + EW_THREADS - 1) / EW_THREADS, 256 * 16); }
-
-#define GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
@@ -1177,7 +1172,7 @@ __global__ void permute_nt_kernel(const f32x4* __restrict__ src, f32x4* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// losses, Adam
+// losses
 // ------------------------------------------------------------------------------------------------
 __global__ void hinge_disc_kernel(const float* __restrict__ s_real, const float* __restrict__ s_gen, float* __restrict__ loss,
                                   float* __restrict__ d_real, float* __restrict__ d_gen, int n_real, int n_gen) {
@@ -1239,306 +1234,6 @@ __global__ __launch_bounds__(256) void grid_cell_finish_kernel(double* __restric
     if (threadIdx.x != 0) return;
     loss[0] = (float)(acc[0] * (double)mult);
     acc[0] = 0.0;
-}
-
-// torch.optim.Adam's update, scalar for scalar (torch/optim/adam.py, _multi_tensor_adam): exp_avg.lerp_(grad, 1 - beta1);
-// exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2); denom = sqrt(exp_avg_sq) / sqrt(bias_correction2) + eps;
-// param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1).  The scalars are formed in double on the host and rounded to
-// float once, as torch does (1 - 0.999 in float arithmetic is 4.7e-5 off).
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                            float w1 /* 1 - beta1 */, float beta2, float w2 /* 1 - beta2 */, float eps, float step_size,
-                            float bc2_sqrt) {
-    GRID_STRIDE(i, n) {
-        const float gi = g[i], m0 = m[i];
-        const float diff = gi - m0;
-        const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);  // at::lerp
-        const float vi = fmaf(w2 * gi, gi, beta2 * v[i]);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    }
-}
-
-// Every tensor of an optimiser in ONE launch: block b works on chunk (b - d.block0) of tensor d, found by bisection over the
-// descriptors' first blocks.  Same per-element arithmetic as adam_kernel (bit-identical updates).
-constexpr int ADAM_CHUNK = 4096;  // elements per block
-__global__ __launch_bounds__(256) void adam_multi_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors, float w1, float beta2, float w2,
-                                                         float eps) {
-    int lo = 0, hi = n_tensors - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {  // last descriptor whose block0 <= b
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const dgmr_adam_desc d = descs[lo];
-    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK, i1 = i0 + ADAM_CHUNK < d.n ? i0 + ADAM_CHUNK : d.n;
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-        const float gi = d.g[i], m0 = d.m[i];
-        const float diff = gi - m0;
-        const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);
-        const float vi = fmaf(w2 * gi, gi, beta2 * d.v[i]);
-        d.m[i] = mi;
-        d.v[i] = vi;
-        d.p[i] -= d.step_size * (mi / (sqrtf(vi) / d.bc2_sqrt + eps));
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// gradient guard: global L2 norm (torch.nn.utils.clip_grad_norm_), clip coefficient, skip on NaN / Inf
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int adam_desc_of_block(const dgmr_adam_desc* __restrict__ descs, int n_tensors, int b) {
-    int lo = 0, hi = n_tensors - 1;
-    while (lo < hi) {  // last descriptor whose block0 <= b
-        const int mid = (lo + hi + 1) >> 1;
-        if (descs[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Fixed-order sum over a 256-thread workgroup: xor butterfly inside each wave64, then the four wave sums in wave order.
-__device__ __forceinline__ double block_sum_f64(double v, double* smem /* 4 doubles */) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((smem[0] + smem[1]) + smem[2]) + smem[3];
-}
-
-// Stage 1, same workgroup -> chunk mapping as adam_multi_kernel.  Thread t owns the four-element groups t, t + 256, t + 512, t + 768 of
-// its chunk and adds their squares in element order, whichever load path brings them in: sixteen-byte loads when the chunk is whole
-// and g is 16-byte aligned, dword loads (bounds-checked, g 4-byte aligned: a view into a flat buffer) otherwise.  Both paths keep all
-// of a lane's loads in flight before the first add.  fp32 -> double is exact and so is the square: one rounding per add.
-__global__ __launch_bounds__(256) void grad_sq_partial_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors,
-                                                              double* __restrict__ partials) {
-    __shared__ double red[4];
-    const int b = blockIdx.x;
-    const dgmr_adam_desc d = descs[adam_desc_of_block(descs, n_tensors, b)];
-    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK;
-    const int64_t left = d.n - i0;  // > 0 by construction of block0
-    const float* __restrict__ g = d.g + i0;
-    float x[ADAM_CHUNK / 256];
-    if (left >= ADAM_CHUNK && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k < ADAM_CHUNK / 1024; ++k) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(g + k * 1024 + threadIdx.x * 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) x[k * 4 + j] = q[j];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < ADAM_CHUNK / 1024; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = k * 1024 + threadIdx.x * 4 + j;
-                x[k * 4 + j] = e < left ? g[e] : 0.f;  // (+0 leaves a sum of squares unchanged)
-            }
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < ADAM_CHUNK / 256; ++k) s += (double)x[k] * (double)x[k];
-    s = block_sum_f64(s, red);
-    if (threadIdx.x == 0) partials[b] = s;
-}
-
-// Stage 2, one workgroup per tensor: thread t adds the tensor's partials t, t + 256, ... in increasing order, then block_sum_f64.
-__global__ __launch_bounds__(256) void grad_sq_tensor_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors, int total_blocks,
-                                                             const double* __restrict__ partials, double* __restrict__ tensor_sq) {
-    __shared__ double red[4];
-    const int t = blockIdx.x;
-    const int b0 = descs[t].block0, b1 = t + 1 < n_tensors ? descs[t + 1].block0 : total_blocks;
-    double s = 0.0;
-    for (int b = b0 + threadIdx.x; b < b1; b += 256) s += partials[b];
-    s = block_sum_f64(s, red);
-    if (threadIdx.x == 0) tensor_sq[t] = s;
-}
-
-// Stage 3, one workgroup: the tensors' sums added one after the other in table order (a few hundred adds; staged through LDS 256 at a
-// time so that the loads are coalesced), then the guard record.  A plain running sum is unchanged by tensors whose gradient is all
-// zero: flat gradient buffers, which give every parameter a (zero) gradient, yield the bits of the run where those have none.
-__global__ __launch_bounds__(256) void grad_guard_finish_kernel(const double* __restrict__ tensor_sq, int n_tensors, float max_norm,
-                                                                int skip_nonfinite, dgmr_grad_guard* __restrict__ guard) {
-    __shared__ double tile[256];
-    double s = 0.0;
-    for (int t0 = 0; t0 < n_tensors; t0 += 256) {
-        tile[threadIdx.x] = t0 + threadIdx.x < n_tensors ? tensor_sq[t0 + threadIdx.x] : 0.0;
-        __syncthreads();
-        if (threadIdx.x == 0)
-#pragma unroll 16
-            for (int k = 0; k < 256; ++k) s += tile[k];
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    const float total_norm = (float)sqrt(s);
-    float coef = 1.f;
-    if (max_norm > 0.f) {  // torch: clamp(max_norm / (total_norm + 1e-6), max=1.0) in float; NaN passes through clamp
-        coef = max_norm / (total_norm + 1e-6f);
-        coef = coef > 1.f ? 1.f : coef;
-    }
-    const int skipped = skip_nonfinite && !isfinite(total_norm) ? 1 : 0;
-    guard->total_norm = total_norm;
-    guard->clip_coef = coef;
-    guard->skipped = skipped;
-    guard->skipped_total += skipped;
-}
-
-// adam_multi_kernel on g * clip_coef (the product rounded to float on its own, as clip_grad_norm_'s g.mul_ stores it); nothing is
-// stored when the guard says skip.  `descs` may be one parameter group's slice of a larger table: blocks count from descs[0].block0.
-__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const dgmr_adam_desc* __restrict__ descs, int n_tensors, float w1,
-                                                                 float beta2, float w2, float eps,
-                                                                 const dgmr_grad_guard* __restrict__ guard) {
-    if (guard->skipped != 0) return;
-    const float coef = guard->clip_coef;
-    const int b = blockIdx.x + descs[0].block0;
-    const dgmr_adam_desc d = descs[adam_desc_of_block(descs, n_tensors, b)];
-    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK, i1 = i0 + ADAM_CHUNK < d.n ? i0 + ADAM_CHUNK : d.n;
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-        const float gi = __fmul_rn(d.g[i], coef), m0 = d.m[i];
-        const float diff = gi - m0;
-        const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);
-        const float vi = fmaf(w2 * gi, gi, beta2 * d.v[i]);
-        d.m[i] = mi;
-        d.v[i] = vi;
-        d.p[i] -= d.step_size * (mi / (sqrtf(vi) / d.bc2_sqrt + eps));
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight EMA (torch.optim.swa_utils.get_ema_multi_avg_fn: ema.lerp_(param, 1 - decay)) inside the Adam launch, and the evaluation swap
-// ------------------------------------------------------------------------------------------------
-// One element of adam_multi_kernel (GUARDED: of adam_multi_guarded_kernel), the same expressions in the same order, followed by
-// Tensor.lerp_ of the shadow towards the float just formed for p (at::lerp's two branches).  e is touched only when has_e.
-template <bool GUARDED>
-__device__ __forceinline__ void adam_ema_element(float g, float coef, float& m, float& v, float& p, float& e, bool has_e, float w1,
-                                                 float beta2, float w2, float eps, float step_size, float bc2_sqrt, float we) {
-    const float gi = GUARDED ? __fmul_rn(g, coef) : g, m0 = m;
-    const float diff = gi - m0;
-    const float mi = w1 < 0.5f ? fmaf(w1, diff, m0) : gi - diff * (1.f - w1);
-    const float vi = fmaf(w2 * gi, gi, beta2 * v);
-    m = mi;
-    v = vi;
-    p -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    if (has_e) {
-        const float pn = p, e0 = e;
-        e = we < 0.5f ? fmaf(we, pn - e0, e0) : pn - (pn - e0) * (1.f - we);
-    }
-}
-
-// adam_multi_kernel / adam_multi_guarded_kernel plus the shadow update in the same pass: 36 bytes per element instead of 28, no second
-// launch and no second read of p.  Same workgroup -> chunk mapping; `descs` (and `ema`, its parallel array of shadow pointers, NULL =
-// no shadow) may be a group's slice of a larger table.  A whole chunk whose p / m / v / shadow pointers are 16-byte aligned moves as
-// f32x4: lane t owns elements 4t .. 4t + 3 of each 1024-element quarter and has the loads of all four quarters in flight before the
-// first store.  g is read the same way when it is aligned and dword by dword when it is a 4-byte aligned view into a flat gradient
-// buffer.  Everything else (a tensor's last chunk, short tensors) takes the bounds-checked dword loop of adam_multi_kernel.
-template <bool GUARDED>
-__global__ __launch_bounds__(256) void adam_multi_ema_kernel(const dgmr_adam_desc* __restrict__ descs, float* const* __restrict__ ema,
-                                                             int n_tensors, float w1, float beta2, float w2, float eps, float we,
-                                                             const dgmr_grad_guard* __restrict__ guard) {
-    float coef = 1.f;
-    if (GUARDED) {
-        if (guard->skipped != 0) return;
-        coef = guard->clip_coef;
-    }
-    const int b = blockIdx.x + descs[0].block0;
-    const int t = adam_desc_of_block(descs, n_tensors, b);
-    const dgmr_adam_desc d = descs[t];
-    const int64_t i0 = (int64_t)(b - d.block0) * ADAM_CHUNK;
-    const int64_t left = d.n - i0;  // > 0 by construction of block0
-    const bool has_e = ema[t] != nullptr;
-    float* __restrict__ p = d.p + i0;
-    float* __restrict__ m = d.m + i0;
-    float* __restrict__ v = d.v + i0;
-    float* __restrict__ e = has_e ? ema[t] + i0 : nullptr;
-    const float* __restrict__ g = d.g + i0;
-    constexpr int Q = ADAM_CHUNK / 1024;
-    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-                            reinterpret_cast<uintptr_t>(e);
-    if (left >= ADAM_CHUNK && (align & 15) == 0) {
-        f32x4 gq[Q], mq[Q], vq[Q], pq[Q], eq[Q];
-        const int lane = threadIdx.x * 4;
-        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-#pragma unroll
-            for (int k = 0; k < Q; ++k) gq[k] = *reinterpret_cast<const f32x4*>(g + k * 1024 + lane);
-        } else {
-#pragma unroll
-            for (int k = 0; k < Q; ++k)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) gq[k][j] = g[k * 1024 + lane + j];
-        }
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-            mq[k] = *reinterpret_cast<const f32x4*>(m + k * 1024 + lane);
-            vq[k] = *reinterpret_cast<const f32x4*>(v + k * 1024 + lane);
-            pq[k] = *reinterpret_cast<const f32x4*>(p + k * 1024 + lane);
-        }
-        if (has_e) {
-#pragma unroll
-            for (int k = 0; k < Q; ++k) eq[k] = *reinterpret_cast<const f32x4*>(e + k * 1024 + lane);
-        }
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float mj = mq[k][j], vj = vq[k][j], pj = pq[k][j], ej = has_e ? eq[k][j] : 0.f;
-                adam_ema_element<GUARDED>(gq[k][j], coef, mj, vj, pj, ej, has_e, w1, beta2, w2, eps, d.step_size, d.bc2_sqrt, we);
-                mq[k][j] = mj;
-                vq[k][j] = vj;
-                pq[k][j] = pj;
-                eq[k][j] = ej;
-            }
-            *reinterpret_cast<f32x4*>(m + k * 1024 + lane) = mq[k];
-            *reinterpret_cast<f32x4*>(v + k * 1024 + lane) = vq[k];
-            *reinterpret_cast<f32x4*>(p + k * 1024 + lane) = pq[k];
-            if (has_e) *reinterpret_cast<f32x4*>(e + k * 1024 + lane) = eq[k];
-        }
-        return;
-    }
-    const int n = left < ADAM_CHUNK ? (int)left : ADAM_CHUNK;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        float mj = m[i], vj = v[i], pj = p[i], ej = has_e ? e[i] : 0.f;
-        adam_ema_element<GUARDED>(g[i], coef, mj, vj, pj, ej, has_e, w1, beta2, w2, eps, d.step_size, d.bc2_sqrt, we);
-        m[i] = mj;
-        v[i] = vj;
-        p[i] = pj;
-        if (has_e) e[i] = ej;
-    }
-}
-
-// p <-> shadow, every tensor in one launch (the evaluation swap: what swa_utils users do with AveragedModel.module, in place here
-// because the modules' caches are keyed on the parameters' addresses).  Reads p, n and block0 of the descriptor only.
-__global__ __launch_bounds__(256) void swap_multi_kernel(const dgmr_adam_desc* __restrict__ descs, float* const* __restrict__ ema,
-                                                         int n_tensors) {
-    const int b = blockIdx.x + descs[0].block0;
-    const int t = adam_desc_of_block(descs, n_tensors, b);
-    if (ema[t] == nullptr) return;
-    const int64_t i0 = (int64_t)(b - descs[t].block0) * ADAM_CHUNK;
-    const int64_t left = descs[t].n - i0;
-    float* __restrict__ p = descs[t].p + i0;
-    float* __restrict__ e = ema[t] + i0;
-    constexpr int Q = ADAM_CHUNK / 1024;
-    if (left >= ADAM_CHUNK && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(e)) & 15) == 0) {
-        f32x4 pq[Q], eq[Q];
-        const int lane = threadIdx.x * 4;
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-            pq[k] = *reinterpret_cast<const f32x4*>(p + k * 1024 + lane);
-            eq[k] = *reinterpret_cast<const f32x4*>(e + k * 1024 + lane);
-        }
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-            *reinterpret_cast<f32x4*>(p + k * 1024 + lane) = eq[k];
-            *reinterpret_cast<f32x4*>(e + k * 1024 + lane) = pq[k];
-        }
-        return;
-    }
-    const int n = left < ADAM_CHUNK ? (int)left : ADAM_CHUNK;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float pi = p[i], ei = e[i];
-        p[i] = ei;
-        e[i] = pi;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1693,8 +1388,6 @@ __global__ __launch_bounds__(64 * CROP_WAVES) void crop_gather_kernel(const T* _
 }
 
 }  // namespace
-
-#define ST ((hipStream_t)stream)
 
 extern "C" int dgmr_spectral_sigma(const float* w, float* u, float* v, float* u_save, float* v_save, float* inv_sigma,
                                    float* scratch, float* tmp, int Cout, int Cin, int taps, float eps, int train, void* stream) {
@@ -2460,79 +2153,6 @@ extern "C" int dgmr_grid_cell_loss(const float* preds, int K, int64_t pred_strid
     hipLaunchKernelGGL(grid_cell_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, ST, preds, K, pred_stride, target, weights, cap,
                        acc, dweight, n, g_deterministic);
     hipLaunchKernelGGL(grid_cell_finish_kernel, dim3(1), dim3(256), 0, ST, acc, loss, mult, g_deterministic ? ew_blocks(n) : 0);
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
-                         int step, void* stream) {
-    DGMR_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "dgmr_adam: bad args");
-    DGMR_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "dgmr_adam: betas (%g, %g) out of [0, 1)", beta1, beta2);
-    const double bc1 = 1.0 - std::pow(beta1, (double)step);
-    const double bc2 = 1.0 - std::pow(beta2, (double)step);
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, ST, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), (float)eps, (float)(lr / bc1), (float)std::sqrt(bc2));
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_adam_chunk(void) { return ADAM_CHUNK; }
-
-extern "C" int dgmr_adam_multi(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2, double eps,
-                               void* stream) {
-    DGMR_CHECK_ARG(descs && n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi: bad args");
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), (float)eps);
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_grad_norm_multi(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double* partials, double* tensor_sq,
-                                    double max_norm, int skip_nonfinite, dgmr_grad_guard* guard, void* stream) {
-    DGMR_CHECK_ARG(descs && partials && tensor_sq && guard, "dgmr_grad_norm_multi: null pointer");
-    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_grad_norm_multi: n_tensors=%d total_blocks=%d must be positive", n_tensors,
-                   total_blocks);
-    DGMR_CHECK_ARG(max_norm == max_norm, "dgmr_grad_norm_multi: max_norm is NaN");
-    hipLaunchKernelGGL(grad_sq_partial_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, partials);
-    hipLaunchKernelGGL(grad_sq_tensor_kernel, dim3(n_tensors), dim3(256), 0, ST, descs, n_tensors, total_blocks, partials, tensor_sq);
-    hipLaunchKernelGGL(grad_guard_finish_kernel, dim3(1), dim3(256), 0, ST, tensor_sq, n_tensors, max_norm > 0.0 ? (float)max_norm : 0.f,
-                       skip_nonfinite, guard);
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_adam_multi_guarded(const dgmr_adam_desc* descs, int n_tensors, int total_blocks, double beta1, double beta2,
-                                       double eps, const dgmr_grad_guard* guard, void* stream) {
-    DGMR_CHECK_ARG(descs && guard, "dgmr_adam_multi_guarded: null pointer");
-    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi_guarded: n_tensors=%d total_blocks=%d must be positive", n_tensors,
-                   total_blocks);
-    hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, n_tensors, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps, guard);
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_adam_multi_ema(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, double beta1,
-                                   double beta2, double eps, double ema_weight, const dgmr_grad_guard* guard, void* stream) {
-    DGMR_CHECK_ARG(descs && ema, "dgmr_adam_multi_ema: null pointer");
-    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_adam_multi_ema: n_tensors=%d total_blocks=%d must be positive", n_tensors,
-                   total_blocks);
-    DGMR_CHECK_ARG(ema_weight >= 0.0 && ema_weight <= 1.0, "dgmr_adam_multi_ema: ema_weight=%g out of [0, 1]", ema_weight);  // (NaN too)
-    if (guard)
-        hipLaunchKernelGGL(adam_multi_ema_kernel<true>, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors, (float)(1.0 - beta1),
-                           (float)beta2, (float)(1.0 - beta2), (float)eps, (float)ema_weight, guard);
-    else
-        hipLaunchKernelGGL(adam_multi_ema_kernel<false>, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors,
-                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)ema_weight, guard);
-    DGMR_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int dgmr_swap_multi(const dgmr_adam_desc* descs, float* const* ema, int n_tensors, int total_blocks, void* stream) {
-    DGMR_CHECK_ARG(descs && ema, "dgmr_swap_multi: null pointer");
-    DGMR_CHECK_ARG(n_tensors > 0 && total_blocks > 0, "dgmr_swap_multi: n_tensors=%d total_blocks=%d must be positive", n_tensors,
-                   total_blocks);
-    hipLaunchKernelGGL(swap_multi_kernel, dim3(total_blocks), dim3(256), 0, ST, descs, ema, n_tensors);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

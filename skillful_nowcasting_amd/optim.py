@@ -12,6 +12,11 @@ class FusedAdam(torch.optim.Optimizer):
     State layout (``step``, ``exp_avg``, ``exp_avg_sq``) matches torch.optim.Adam so optimiser checkpoints
     interchange.  Parameters that received no gradient are skipped, like torch does.
 
+    Every step() makes ONE descriptor table over every parameter with a gradient in ALL groups (one pinned upload) and one Adam launch
+    per group on that group's slice of it: plain, guarded and EMA steps differ only in the entry point.  For an optimiser with one
+    group - both of DGMR's - that is the upload and the launch it always issued; one with several groups makes one upload per step
+    where it used to make one per group.
+
     Gradient guard (off by default; with both options at their defaults step() issues exactly the launches it always did):
 
     * ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_(all parameters of this optimiser, max_grad_norm)`` applied inside the Adam
@@ -21,9 +26,8 @@ class FusedAdam(torch.optim.Optimizer):
       (the step never waits for the device, so the host cannot know; a device-side counter per parameter is not worth it).
 
     Both are plain attributes (not ``param_groups`` keys: ``state_dict()`` stays interchangeable with torch.optim.Adam) and may be
-    changed between steps.  With either set, step() makes one descriptor table over every parameter with a gradient in ALL groups,
-    one norm pass over it (dgmr_grad_norm_multi: one extra read of the gradients, deterministic, no host synchronisation) and one
-    dgmr_adam_multi_guarded launch per group.  Results stay on the device, as views into the guard's scratch that the next guarded
+    changed between steps.  With either set, step() adds one norm pass over the table (dgmr_grad_norm_multi: one extra read of the
+    gradients, deterministic, no host synchronisation) and launches dgmr_adam_multi_guarded on the slices.  Results stay on the device, as views into the guard's scratch that the next guarded
     step overwrites: ``last_grad_norm``, ``last_clip_coef``, ``skipped_steps`` (running count), ``last_tensor_grad_norms`` (float64,
     in the order of ``last_guarded_params``).  ``nonfinite_parameters()`` is the only method that synchronises.
 
@@ -119,10 +123,10 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         written = []
-        rows, slices = [], []  # guarded: one table over all groups, (first row, rows, b1, b2, eps) per group
+        rows, slices = [], []  # one table over all groups, (first row, rows, b1, b2, eps) per group
         for group in self.param_groups:
             b1, b2 = group["betas"]
-            todo = []
+            first = len(rows)
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -138,16 +142,13 @@ class FusedAdam(torch.optim.Optimizer):
                 if g.stride() != p.stride():  # kernels index raw storage: bring the gradient to the parameter's layout
                     g = torch.empty_like(p).copy_(g)
                 if self.multi_tensor:
-                    todo.append((p, g, st, group["lr"], b1, b2))
+                    rows.append((p, g, st, group["lr"], b1, b2))
                 else:
                     ops.adam_update(p, g, st["exp_avg"], st["exp_avg_sq"], st["step"], group["lr"], b1, b2, group["eps"])
-            if todo and guarded:
-                slices.append((len(rows), len(todo), b1, b2, group["eps"]))
-                rows += todo
-            elif todo:
-                self._step_multi(todo, b1, b2, group["eps"], ema_w)
+            if len(rows) > first:
+                slices.append((first, len(rows) - first, b1, b2, group["eps"]))
         if rows:
-            self._step_guarded(rows, slices, ema_w)
+            self._step_multi(rows, slices, guarded, ema_w)
         if ema_w is not None and written:
             self.ema_num_updates += 1
         ops._core.note_optimizer_step(written)  # (the images of THESE weights are stale; everything else keeps its caches)
@@ -212,16 +213,24 @@ class FusedAdam(torch.optim.Optimizer):
         done.record()
         return dev, block0
 
-    def _step_multi(self, todo, b1, b2, eps, ema_w=None):
-        """The tensors of one parameter group: one table upload, then ONE launch."""
+    def _step_multi(self, rows, slices, guarded, ema_w):
+        """One table over all groups (one upload), the norm pass over all of it if the guard is on, then ONE Adam launch on every
+        group's slice."""
         from ._lib import ADAM_DESC_DTYPE
 
-        dev, block0 = self._upload_table(todo, ema=ema_w is not None)
-        if ema_w is None:
-            ops.call("dgmr_adam_multi", dev.data_ptr(), len(todo), block0[-1], float(b1), float(b2), float(eps), ops._stream())
-        else:
-            ops.call("dgmr_adam_multi_ema", dev.data_ptr(), dev.data_ptr() + len(todo) * ADAM_DESC_DTYPE.itemsize, len(todo), block0[-1],
-                     float(b1), float(b2), float(eps), ema_w, None, ops._stream())
+        dev, block0 = self._upload_table(rows, ema=ema_w is not None)
+        stream = ops._stream()
+        guard = self._norm_pass(dev, rows, block0[-1], stream) if guarded else None
+        shadows = dev.data_ptr() + len(rows) * ADAM_DESC_DTYPE.itemsize  # (the shadows' pointers follow the descriptors)
+        for first, count, b1, b2, eps in slices:
+            descs = dev.data_ptr() + first * ADAM_DESC_DTYPE.itemsize
+            args = (count, block0[first + count] - block0[first], float(b1), float(b2), float(eps))
+            if ema_w is not None:
+                ops.call("dgmr_adam_multi_ema", descs, shadows + 8 * first, *args, ema_w, guard, stream)
+            elif guarded:
+                ops.call("dgmr_adam_multi_guarded", descs, *args, guard, stream)
+            else:
+                ops.call("dgmr_adam_multi", descs, *args, stream)
 
     # ------------------------------------------------------------------------------------------
     # weight EMA
@@ -299,13 +308,9 @@ class FusedAdam(torch.optim.Optimizer):
     # ------------------------------------------------------------------------------------------
     # gradient guard
     # ------------------------------------------------------------------------------------------
-    def _step_guarded(self, rows, slices, ema_w=None):
-        """One table over all groups (one upload), the norm pass over all of it, then the guarded Adam launch on every group's slice."""
-        from ._lib import ADAM_DESC_DTYPE
-
-        dev, block0 = self._upload_table(rows, ema=ema_w is not None)
-        n, blocks = len(rows), block0[-1]
-        device = rows[0][0].device
+    def _norm_pass(self, dev, rows, blocks, stream):
+        """dgmr_grad_norm_multi over the whole table -> the device address of the guard record the Adam launches read."""
+        n, device = len(rows), rows[0][0].device
         d = self.__dict__
         if d.get("_guard") is None:  # 16 bytes, dgmr_grad_guard; allocated once (skipped_total lives in it)
             d["_guard"] = torch.zeros(4, dtype=torch.int32, device=device)
@@ -313,19 +318,10 @@ class FusedAdam(torch.optim.Optimizer):
             d["_partials"] = torch.empty(blocks, dtype=torch.float64, device=device)
         if d.get("_tensor_sq") is None or d["_tensor_sq"].numel() < n:
             d["_tensor_sq"] = torch.empty(n, dtype=torch.float64, device=device)
-        guard = d["_guard"]
-        stream = ops._stream()
         ops.call("dgmr_grad_norm_multi", dev.data_ptr(), n, blocks, d["_partials"].data_ptr(), d["_tensor_sq"].data_ptr(),
-                 float(self.max_grad_norm or 0.0), int(bool(self.skip_nonfinite)), guard.data_ptr(), stream)
-        for first, count, b1, b2, eps in slices:
-            descs = dev.data_ptr() + first * ADAM_DESC_DTYPE.itemsize
-            if ema_w is None:
-                ops.call("dgmr_adam_multi_guarded", descs, count, block0[first + count] - block0[first], float(b1), float(b2),
-                         float(eps), guard.data_ptr(), stream)
-            else:
-                ops.call("dgmr_adam_multi_ema", descs, dev.data_ptr() + n * ADAM_DESC_DTYPE.itemsize + 8 * first, count,
-                         block0[first + count] - block0[first], float(b1), float(b2), float(eps), ema_w, guard.data_ptr(), stream)
+                 float(self.max_grad_norm or 0.0), int(bool(self.skip_nonfinite)), d["_guard"].data_ptr(), stream)
         d["_guarded_params"] = [r[0] for r in rows]
+        return d["_guard"].data_ptr()
 
     @property
     def last_grad_norm(self):

@@ -2,7 +2,7 @@
 Tensor.lerp_ of a shadow towards the new parameter, one pass) and dgmr_swap_multi (the evaluation swap), from the kernels up to
 DGMR.ema_scope().
 
-Tensor set: that of test_gpu_grad_guard.py - tensors shorter and longer than a workgroup's chunk (4096), one that ends five elements
+Tensor set (adam_recipe.py): tensors shorter and longer than a workgroup's chunk (4096), one that ends five elements
 past a chunk edge, a channels-last conv weight, a tensor without a gradient in two steps.  Five steps, gradients scaled
 10 ** (step % 3 - 1).
 
@@ -19,40 +19,11 @@ import numpy as np
 import pytest
 import torch
 
+import adam_recipe as R
+
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(3,), (4097,), (16, 8, 3, 3), (20000,), (1,), (129, 65), (3 * 4096 + 5,)]
-NO_GRAD = (3, (1, 2))  # tensor 3 gets no gradient in steps 1 and 2
 UNIT = 2.0 ** -22  # four fp32 roundings of 2^-24 each, per update and unit of magnitude
-
-
-def _params(seed=12):
-    torch.manual_seed(seed)
-    ps = [torch.randn(s, device="cuda").requires_grad_(True) for s in SHAPES]
-    ps[2].data = ps[2].data.contiguous(memory_format=torch.channels_last)
-    return ps
-
-
-def _grads(ps, steps, seed=100):
-    """[step][tensor] -> gradient (None: no gradient), scaled 10 ** (step % 3 - 1)"""
-    out = []
-    for step in range(steps):
-        torch.manual_seed(seed + step)
-        row = []
-        for i, p in enumerate(ps):
-            g = torch.randn_like(p) * (10.0 ** (step % 3 - 1))
-            row.append(None if i == NO_GRAD[0] and step in NO_GRAD[1] else g)
-        out.append(row)
-    return out
-
-
-def _set_grads(ps, row):
-    for p, g in zip(ps, row):
-        p.grad = None if g is None else g.clone(memory_format=torch.preserve_format)
-
-
-def _state(opt, ps):
-    return [t.detach().clone() for p in ps for t in (p, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])]
 
 
 def _shadows(opt, ps):
@@ -63,17 +34,17 @@ def _run(steps=5, poison=None, **kw):
     """-> dict(p0: parameters before the first step, states: _state after every step, shadows: after every step (EMA on), opt, ps)"""
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    ps = _params()
-    grads = _grads(ps, steps)
+    ps = R.params()
+    grads = R.grads(ps, steps)
     if poison is not None:
         step, tensor, index, value = poison
         grads[step][tensor].view(-1)[index] = value
     opt = FusedAdam(ps, lr=2e-3, **kw)
     rec = dict(p0=[p.detach().clone() for p in ps], states=[], shadows=[], grads=grads, opt=opt, ps=ps)
     for row in grads:
-        _set_grads(ps, row)
+        R.set_grads(ps, row)
         opt.step()
-        rec["states"].append(_state(opt, ps))
+        rec["states"].append(R.state(opt, ps))
         if opt.ema_decay is not None:
             rec["shadows"].append(_shadows(opt, ps))
     torch.cuda.synchronize()
@@ -109,7 +80,7 @@ def _check_recurrence(p0, snapshots, shadows, weights, stepped, what=""):
 
 
 def _stepped(k, i):
-    return not (i == NO_GRAD[0] and k in NO_GRAD[1])
+    return not (i == R.NO_GRAD[0] and k in R.NO_GRAD[1])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -148,7 +119,7 @@ def test_average_against_float64(decay):
     _check_recurrence(run["p0"], snaps, run["shadows"], [_w(decay)] * 5, _stepped, f"decay {decay}")
     if decay == 0.0:
         for k in range(5):
-            for i in range(len(SHAPES)):
+            for i in range(len(R.SHAPES)):
                 if _stepped(k, i):
                     assert torch.equal(run["shadows"][k][i], snaps[k][i]), (k, i)
     else:  # the average is neither the parameter nor its starting point
@@ -197,7 +168,7 @@ def test_skipped_step_leaves_the_average(bad):
 # ------------------------------------------------------------------------------------------------
 def test_shadow_of_a_parameter_without_gradient_does_not_move():
     run = _run(betas=(0.9, 0.99), ema_decay=0.9)
-    i = NO_GRAD[0]
+    i = R.NO_GRAD[0]
     sh = [s[i] for s in run["shadows"]]
     assert torch.equal(sh[0], sh[1]) and torch.equal(sh[1], sh[2])  # steps 1 and 2: not in the table
     assert not torch.equal(sh[2], sh[3]) and not torch.equal(sh[3], sh[4])
@@ -211,13 +182,13 @@ def test_swap_exchanges_and_restores():
     from skillful_nowcasting_amd import ops
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    ps = _params()
+    ps = R.params()
     torch.manual_seed(5)
     lone = [torch.randn(5000, device="cuda").requires_grad_(True), torch.randn(7, device="cuda").requires_grad_(True)]
     every = [lone[0]] + ps + [lone[1]]  # parameters that never get a gradient: no shadow, at both ends of the list
     opt = FusedAdam(every, lr=2e-3, betas=(0.9, 0.99), ema_decay=0.5)
-    for row in _grads(ps, 3):
-        _set_grads(ps, row)
+    for row in R.grads(ps, 3):
+        R.set_grads(ps, row)
         opt.step()
     assert all(opt.ema(p) is None for p in lone)
     p_old = [p.detach().clone() for p in every]
@@ -284,6 +255,73 @@ def test_null_shadow_entries_are_skipped():
         assert torch.equal(pb[i], e_now[i]) and torch.equal(eb[i], p_old[i]), i
 
 
+def test_adam_multi_on_a_slice_of_a_table():
+    """dgmr_adam_multi on descs + 1 of a three-row table (block0 of the slice's first row is not 0) against dgmr_adam_multi on a table
+    built for those two rows alone; the row in front of the slice is left alone."""
+    from skillful_nowcasting_amd import _lib, ops
+
+    chunk = int(_lib.load().dgmr_adam_chunk())
+    shapes = [(4096 + 3,), (2 * 4096,), (100,)]
+
+    def make():
+        torch.manual_seed(31)
+        return [[torch.randn(s, device="cuda") for s in shapes] for _ in range(3)] + [[torch.rand(s, device="cuda") for s in shapes]]
+
+    def table(rows, p, g, m, v):
+        tab = np.zeros(len(rows), dtype=_lib.ADAM_DESC_DTYPE)
+        block = 0
+        for k, i in enumerate(rows):
+            tab[k] = (p[i].data_ptr(), g[i].data_ptr(), m[i].data_ptr(), v[i].data_ptr(), p[i].numel(), block, np.float32(2e-3 / 0.1),
+                      np.float32(0.1), 0)
+            block += (p[i].numel() + chunk - 1) // chunk
+        return torch.from_numpy(tab.view(np.uint8)).cuda(), block
+
+    a, b = make(), make()
+    first = [t[0].clone() for t in a]
+    ta, blocks3 = table([0, 1, 2], *a)
+    tb, blocks2 = table([1, 2], *b)
+    assert blocks3 == 5 and blocks2 == 3  # the slice's first row starts at block 2
+    ops.call("dgmr_adam_multi", ta.data_ptr() + _lib.ADAM_DESC_DTYPE.itemsize, 2, blocks2, 0.9, 0.99, 1e-8, ops._stream())
+    ops.call("dgmr_adam_multi", tb.data_ptr(), 2, blocks2, 0.9, 0.99, 1e-8, ops._stream())
+    torch.cuda.synchronize()
+    for j, (u, v) in enumerate(zip(a, b)):  # p, g, m, v
+        assert torch.equal(u[0], first[j]), j
+        assert torch.equal(u[1], v[1]) and torch.equal(u[2], v[2]), j
+    assert not torch.equal(a[0][1], make()[0][1])  # the slice was updated
+
+
+@pytest.mark.parametrize("ema", [None, 0.9], ids=["plain", "ema"])
+def test_two_groups_with_their_own_hyperparameters(ema):
+    """Two parameter groups that differ in lr, betas and eps (one table, one launch per slice, each with its group's scalars) against
+    one dgmr_adam launch per tensor: parameters and moments bit for bit after every step, with and without EMA; the shadows against
+    the float64 recurrence."""
+    from skillful_nowcasting_amd.optim import FusedAdam
+
+    def make(**kw):
+        ps = R.params()
+        groups = [dict(params=ps[:3]), dict(params=ps[3:], lr=5e-3, betas=(0.5, 0.9), eps=1e-6)]
+        return ps, FusedAdam(groups, lr=2e-3, betas=(0.9, 0.99), **kw)
+
+    (pa, oa), (pb, ob) = make(ema_decay=ema), make()
+    ob.multi_tensor = False
+    p0 = [p.detach().clone() for p in pa]
+    snaps, shadows = [], []
+    for k, row in enumerate(R.grads(pa, 5)):
+        R.set_grads(pa, row)
+        R.set_grads(pb, row)
+        oa.step()
+        ob.step()
+        sa, sb = R.state(oa, pa), R.state(ob, pb)
+        bad = [i for i, (u, v) in enumerate(zip(sa, sb)) if not torch.equal(u, v)]
+        assert not bad, (k, bad)
+        snaps.append(sa[0::3])
+        if ema is not None:
+            shadows.append(_shadows(oa, pa))
+    assert [oa.state[p]["step"] for p in pa] == [ob.state[p]["step"] for p in pb] == [5, 5, 5, 3, 5, 5, 5]
+    if ema is not None:
+        _check_recurrence(p0, snaps, shadows, [_w(ema)] * 5, _stepped, "two groups")
+
+
 # ------------------------------------------------------------------------------------------------
 # 7. flat gradient buffers
 # ------------------------------------------------------------------------------------------------
@@ -292,42 +330,53 @@ def _run_layout(layout, steps=5):
     (4-byte aligned only), the way ddp.FlatGrads makes them; the buffer is opt.flat_grads, as under attach_data_parallel()."""
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    ps = _params()
-    grads = _grads(ps, steps)
+    ps = R.params()
+    grads = R.grads(ps, steps)
     opt = FusedAdam(ps, lr=2e-3, betas=(0.9, 0.99), max_grad_norm=30.0, skip_nonfinite=True, ema_decay=0.9)
     views = None
     if layout == "flat":
-        offs, off = [], 1
-        for p in ps:
-            offs.append(off)
-            off += p.numel()
-            off += 1 - off % 2  # the next odd offset
-        flat = torch.zeros(off, device="cuda")
-        opt.flat_grads = flat
-        views = [flat[o:o + p.numel()].as_strided(p.shape, p.stride()) for o, p in zip(offs, ps)]
-        assert all(v.data_ptr() % 16 != 0 and v.data_ptr() % 4 == 0 for v in views)
+        opt.flat_grads, views = R.odd_views(ps)
     for row in grads:
         opt.zero_grad()
         if views is None:
-            _set_grads(ps, row)
+            R.set_grads(ps, row)
         else:
             for p, v, g in zip(ps, views, row):
                 p.grad = None if g is None else v.copy_(g)
         opt.step()
     torch.cuda.synchronize()
-    return _state(opt, ps), _shadows(opt, ps)
+    return R.state(opt, ps), _shadows(opt, ps)
 
 
 def test_flat_gradient_buffers_give_the_same_bits():
     """The sixteen-byte path with a dword-aligned gradient (guard on, as under attach_data_parallel() with a clip norm): parameters,
     moments and shadows agree bit for bit with the run on separate, 16-byte aligned gradient tensors."""
     (sa, ea), (sb, eb) = _run_layout("separate"), _run_layout("flat")
-    for i in range(len(SHAPES)):
+    for i in range(len(R.SHAPES)):
         for j in range(3):
             assert torch.equal(sa[3 * i + j], sb[3 * i + j]), (i, j)
         assert torch.equal(ea[i], eb[i]), i
     (sc, ec) = _run_layout("flat")
     assert all(torch.equal(u, v) for u, v in zip(sb + eb, sc + ec))
+
+
+@pytest.mark.parametrize("mode", list(R.MODES))
+def test_misaligned_parameters_give_the_same_bits(mode):
+    """Parameters that are leaf views at odd element offsets into one flat buffer (4-byte aligned only; moments and shadows are
+    allocated on their own): the dword walk of every chunk, against the recipe on separately allocated parameters - bit for bit on
+    every parameter, moment and shadow (and the guard's norm and coefficient) after each of five steps, after swap_ema() and after
+    swapping back."""
+    want, got = R.run(mode, "separate"), R.run(mode, "flat_params")
+    assert len(want) == len(got) == 7
+    for k, (a, b) in enumerate(zip(want, got)):
+        assert len(a) == len(b) >= 3 * len(R.SHAPES)
+        bad = [i for i, (u, v) in enumerate(zip(a, b)) if not torch.equal(u, v)]
+        assert not bad, (mode, "snapshot", k, bad)
+    n = len(R.SHAPES)
+    if "ema" in mode:  # the swap did exchange parameters and shadows, and the second one put them back
+        assert all(torch.equal(got[5][3 * i], got[4][3 * n + i]) and torch.equal(got[5][3 * n + i], got[4][3 * i]) for i in range(n))
+        assert all(not torch.equal(got[5][3 * i], got[4][3 * i]) for i in range(n))
+    assert all(torch.equal(u, v) for u, v in zip(got[6], got[4]))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -366,7 +415,7 @@ def test_ema_tables_survive_a_gpu_backlog(guard):
             p.grad = g
         ob.step()
         torch.cuda.synchronize()
-    for i, (u, v) in enumerate(zip(_state(oa, pa) + _shadows(oa, pa), _state(ob, pb) + _shadows(ob, pb))):
+    for i, (u, v) in enumerate(zip(R.state(oa, pa) + _shadows(oa, pa), R.state(ob, pb) + _shadows(ob, pb))):
         assert torch.equal(u, v), i
     assert all(not torch.equal(oa.ema(p), p) for p in pa)
 
@@ -379,7 +428,7 @@ def test_ema_state_dict_round_trip_on_the_device():
     run = _run(steps=3, betas=(0.9, 0.99), ema_decay=0.9)
     saved = run["opt"].ema_state_dict()
     adam = copy.deepcopy(run["opt"].state_dict())  # (state_dict() hands out the live moment tensors)
-    assert saved["num_updates"] == 3 and sorted(saved["shadows"]) == list(range(len(SHAPES)))
+    assert saved["num_updates"] == 3 and sorted(saved["shadows"]) == list(range(len(R.SHAPES)))
     host = [torch.nn.Parameter(p.detach().cpu()) for p in run["ps"]]
     opt = FusedAdam(host, lr=2e-3, betas=(0.9, 0.99), ema_decay=0.9)
     opt.load_ema_state_dict({"num_updates": saved["num_updates"], "shadows": {i: t.cpu().contiguous() for i, t in saved["shadows"].items()}})
@@ -392,8 +441,8 @@ def test_ema_state_dict_round_trip_on_the_device():
         assert e.is_cuda and e.stride() == q.stride() and torch.equal(e, run["opt"].ema(q))
     torch.manual_seed(77)
     row = [torch.randn_like(q) for q in run["ps"]]
-    _set_grads(run["ps"], row)
-    _set_grads(host, row)
+    R.set_grads(run["ps"], row)
+    R.set_grads(host, row)
     run["opt"].step()
     opt.step()
     assert opt.ema_num_updates == 4 == run["opt"].ema_num_updates

@@ -2,60 +2,30 @@
 deterministic, independent of the gradients' layout) and dgmr_adam_multi_guarded (Adam on g * clip_coef, nothing stored on a skipped
 step), from the kernels up to DGMR.training_step.
 
-Tensor set: that of test_fused_adam_multi_tensor_equals_per_tensor_launches plus one that ends five elements past a chunk edge -
-tensors shorter and longer than a workgroup's chunk (4096), a channels-last conv weight, a tensor without a gradient in two steps.
+Tensor set: adam_recipe.py.
 """
 import pytest
 import torch
 
+import adam_recipe as R
+
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(3,), (4097,), (16, 8, 3, 3), (20000,), (1,), (129, 65), (3 * 4096 + 5,)]
-NO_GRAD = (3, (1, 2))  # tensor 3 gets no gradient in steps 1 and 2
 ULP2 = 2.0 ** -22  # two fp32 ulps: the squares are exact in double, the double sums add ~ n * 2^-53, one rounding to float
-
-
-def _params(seed=12):
-    torch.manual_seed(seed)
-    ps = [torch.randn(s, device="cuda").requires_grad_(True) for s in SHAPES]
-    ps[2].data = ps[2].data.contiguous(memory_format=torch.channels_last)
-    return ps
-
-
-def _grads(ps, steps, seed=100):
-    """[step][tensor] -> gradient (None: no gradient), scaled 10 ** (step % 3 - 1)"""
-    out = []
-    for step in range(steps):
-        torch.manual_seed(seed + step)
-        row = []
-        for i, p in enumerate(ps):
-            g = torch.randn_like(p) * (10.0 ** (step % 3 - 1))
-            row.append(None if i == NO_GRAD[0] and step in NO_GRAD[1] else g)
-        out.append(row)
-    return out
-
-
-def _set_grads(ps, row):
-    for p, g in zip(ps, row):
-        p.grad = None if g is None else g.clone(memory_format=torch.preserve_format)
 
 
 def _norm64(row):
     return torch.linalg.vector_norm(torch.cat([g.double().flatten() for g in row if g is not None])).item()
 
 
-def _state(opt, ps):
-    return [t.detach().clone() for p in ps for t in (p, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])]
-
-
 def test_norm_against_float64():
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    ps = _params()
-    grads = _grads(ps, 5)
+    ps = R.params()
+    grads = R.grads(ps, 5)
     opt = FusedAdam(ps, lr=2e-3, betas=(0.0, 0.999), max_grad_norm=1.0)
     for step, row in enumerate(grads):
-        _set_grads(ps, row)
+        R.set_grads(ps, row)
         opt.step()
         with_grad = [i for i, g in enumerate(row) if g is not None]
         assert [id(p) for p in opt.last_guarded_params] == [id(ps[i]) for i in with_grad], step  # grad None is left out, as torch does
@@ -79,39 +49,32 @@ def _run_layout(layout, grads_of, steps=5):
     the way ddp.FlatGrads makes them."""
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    ps = _params()
+    ps = R.params()
     grads = grads_of(ps)
     opt = FusedAdam(ps, lr=2e-3, betas=(0.9, 0.99), max_grad_norm=30.0, skip_nonfinite=True)
     views = None
     if layout == "flat":
-        offs, off = [], 1
-        for p in ps:
-            offs.append(off)
-            off += p.numel()
-            off += 1 - off % 2  # the next odd offset
-        flat = torch.zeros(off, device="cuda")
-        views = [flat[o:o + p.numel()].as_strided(p.shape, p.stride()) for o, p in zip(offs, ps)]
-        assert all(v.data_ptr() % 16 != 0 and v.data_ptr() % 4 == 0 for v in views)
+        views = R.odd_views(ps)[1]
     seen = []
     for row in grads[:steps]:
         if views is None:
-            _set_grads(ps, row)
+            R.set_grads(ps, row)
         else:
             for p, v, g in zip(ps, views, row):
                 p.grad = None if g is None else v.copy_(g)
         opt.step()
         seen += [opt.last_grad_norm.clone(), opt.last_clip_coef.clone()]
     torch.cuda.synchronize()
-    return seen + _state(opt, ps)
+    return seen + R.state(opt, ps)
 
 
 def test_layout_independence_and_determinism():
     """Separate gradient tensors (16-byte aligned: the vector-load path) and odd-offset views into a flat buffer (dword loads) sum the
     same elements in the same order: norm, coefficient, parameters and moments agree bit for bit, and so do two runs of one layout."""
-    a = _run_layout("separate", lambda ps: _grads(ps, 5))
-    b = _run_layout("flat", lambda ps: _grads(ps, 5))
-    a2 = _run_layout("separate", lambda ps: _grads(ps, 5))
-    b2 = _run_layout("flat", lambda ps: _grads(ps, 5))
+    a = _run_layout("separate", lambda ps: R.grads(ps, 5))
+    b = _run_layout("flat", lambda ps: R.grads(ps, 5))
+    a2 = _run_layout("separate", lambda ps: R.grads(ps, 5))
+    b2 = _run_layout("flat", lambda ps: R.grads(ps, 5))
     coefs = [t.item() for t in a[1:10:2]]
     assert min(coefs) < 0.5 and max(coefs) == 1.0, coefs  # the clip is active in some steps, off in others
     for what, x, y in (("layouts", a, b), ("separate twice", a, a2), ("flat twice", b, b2)):
@@ -122,17 +85,17 @@ def test_layout_independence_and_determinism():
 def test_inactive_clip_is_the_identity():
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    pa, pb = _params(), _params()
-    grads = _grads(pa, 5)
+    pa, pb = R.params(), R.params()
+    grads = R.grads(pa, 5)
     oa = FusedAdam(pa, lr=2e-3, betas=(0.9, 0.99))
     ob = FusedAdam(pb, lr=2e-3, betas=(0.9, 0.99), max_grad_norm=1e30)
     for step, row in enumerate(grads):
-        _set_grads(pa, row)
-        _set_grads(pb, row)
+        R.set_grads(pa, row)
+        R.set_grads(pb, row)
         oa.step()
         ob.step()
         assert ob.last_clip_coef.item() == 1.0, step
-        for i, (u, v) in enumerate(zip(_state(oa, pa), _state(ob, pb))):
+        for i, (u, v) in enumerate(zip(R.state(oa, pa), R.state(ob, pb))):
             assert torch.equal(u, v), (step, i)
     assert oa.last_grad_norm is None  # the plain optimiser never ran the guard
 
@@ -144,8 +107,8 @@ def test_active_clip_matches_torch(betas):
     the test cannot pass with the clip missing."""
     from skillful_nowcasting_amd.optim import FusedAdam
 
-    p_ref, p_got = _params(), _params()
-    grads = _grads(p_ref, 6)
+    p_ref, p_got = R.params(), R.params()
+    grads = R.grads(p_ref, 6)
     norms = sorted(_norm64(row) for row in grads)
     max_norm = 1.5 * norms[3]  # above the four smaller norms, far below the two at gradient scale 10
     want = [min(1.0, max_norm / (_norm64(row) + 1e-6)) for row in grads]
@@ -154,8 +117,8 @@ def test_active_clip_matches_torch(betas):
     got = FusedAdam(p_got, lr=3e-3, betas=betas, max_grad_norm=max_norm)
     coefs = []
     for step, row in enumerate(grads):
-        _set_grads(p_ref, row)
-        _set_grads(p_got, row)
+        R.set_grads(p_ref, row)
+        R.set_grads(p_got, row)
         torch.nn.utils.clip_grad_norm_(p_ref, max_norm)
         ref.step()
         got.step()
@@ -177,18 +140,18 @@ def test_skip_on_nonfinite_gradient(bad):
     from skillful_nowcasting_amd.optim import FusedAdam
 
     def poisoned(ps):
-        grads = _grads(ps, 5)
+        grads = R.grads(ps, 5)
         grads[2][1].view(-1)[4096] = bad  # step 3, the last element of tensor 1: alone in its chunk
         return grads
 
-    ps = _params()
+    ps = R.params()
     grads = poisoned(ps)
     opt = FusedAdam(ps, lr=2e-3, betas=(0.9, 0.99), max_grad_norm=30.0, skip_nonfinite=True)
     before = None
     for step, row in enumerate(grads):
-        _set_grads(ps, row)
+        R.set_grads(ps, row)
         opt.step()
-        now = _state(opt, ps)
+        now = R.state(opt, ps)
         if step == 2:
             assert all(torch.equal(u, v) for u, v in zip(before, now)), "a skipped step stored something"
             assert opt.skipped_steps.item() == 1
@@ -206,10 +169,10 @@ def test_skip_on_nonfinite_gradient(bad):
     assert [opt.state[p]["step"] for p in ps] == [5, 5, 5, 3, 5, 5, 5]  # the host counter follows attempted steps
 
     # the default is torch's: garbage in, garbage out
-    ps = _params()
+    ps = R.params()
     opt = FusedAdam(ps, lr=2e-3, betas=(0.9, 0.99), max_grad_norm=30.0)
     for row in poisoned(ps)[:3]:
-        _set_grads(ps, row)
+        R.set_grads(ps, row)
         opt.step()
     assert opt.skipped_steps.item() == 0
     assert not torch.isfinite(ps[1]).all().item()
@@ -254,7 +217,7 @@ def test_guarded_descriptor_tables_survive_a_gpu_backlog():
     assert min(coefs) < 0.2 and max(coefs) == 1.0, coefs
     for k, (u, v) in enumerate(zip(norms_a, norms_b)):
         assert torch.equal(u, v), k
-    for i, (u, v) in enumerate(zip(_state(oa, pa), _state(ob, pb))):
+    for i, (u, v) in enumerate(zip(R.state(oa, pa), R.state(ob, pb))):
         assert torch.equal(u, v), i
     # group 2 has its own lr and betas: the slices were launched with their own hyper-parameters
     ref = torch.optim.Adam(make()[0], lr=1e-3, betas=(0.0, 0.999))
