@@ -252,7 +252,10 @@ int dgmr_conv_wgrad_plan(dgmr_wgrad_args* a);
  * skipped; otherwise [groups], zeroed by the caller / the previous finalize).  groups <= 128.
  * ABI 11: `dot` holds dgmr_wgrad_dot_floats(groups) floats - `groups` normally; in deterministic mode groups * (1 + 1024): the
  * workgroups leave their partial dots in rows of their own behind the first `groups` floats and one thread per group adds them up in
- * order (otherwise they meet in float atomics). */
+ * order (otherwise they meet in float atomics).
+ * The slabs are CONSUMED: for narrow weights (numel <= 8192 with at least four slabs per group) a first launch over (group, element
+ * block) sums each group's slabs - in the order of the single launch, so the results are the same bits - in place into the group's
+ * first slab, and the reduce then reads one slab per group; `partial` must be writable and holds no usable values afterwards. */
 int dgmr_wgrad_dot_floats(int groups);
 int dgmr_wgrad_reduce(const float* partial, int nsplit, int groups, int64_t numel, const float* w, const float* scale, float* g,
                       float* dot, void* stream);
@@ -620,7 +623,11 @@ int dgmr_conv_tune(int variant, int ksplit, int window, int wgrad_window);
  * wave-specialised weight-gradient kernel without its matrix work (the loaders' time alone); 256 (round 5) = phase launches of the
  * upsampling convs with one workgroup per ROW parity that computes both column parities from one staged halo, instead of one
  * workgroup per output-pixel parity (conv_win_glds.h PAIR; same results bit for bit - tests/test_gpu_kernels.py; measured no faster,
- * so it is not the default: DGMR_PHASE_PAIR=1 switches it on for a whole process). */
+ * so it is not the default: DGMR_PHASE_PAIR=1 switches it on for a whole process).  512 = the streaming 1x1 kernel writes BatchNorm
+ * partial sums from its epilogue (stats_out) and dgmr_conv_stats_rows answers for it (DGMR_CONV1X1_STATS=1 for a whole process; off by
+ * default); 1024 = dgmr_wgrad_reduce[_slice] never take their two-stage path (DGMR_WGRAD_NARROW=0; same bits either way); 2048 =
+ * dgmr_sn_wgrad_finalize uses its one-thread-per-element kernel (DGMR_SN_FINALIZE_TILED=0; same bits either way); 4096 = dispatch probe:
+ * the LDS-tiled finalize kernel, where dgmr_sn_wgrad_finalize launches it, returns at once and gw keeps its values (garbage by design). */
 int dgmr_debug_flags(int flags);
 
 #ifdef __cplusplus

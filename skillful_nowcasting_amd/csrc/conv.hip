@@ -482,10 +482,14 @@ constexpr int WG_MAX_GROUPS = 128;
 // (cs == ct, coff == 0: j == i).
 // (two workgroups per CU = 256 registers per lane: the MAXG running dot products plus the 16-byte lanes spilled 636 bytes per lane
 //  under the compiler's own occupancy target of four)
-template <int MAXG, bool VEC4 = true>
+template <int MAXG, bool VEC4 = true, bool STRIDED = false>
 __global__ __launch_bounds__(256, 2) void wgrad_reduce_kernel(const float* __restrict__ partial, int nsplit, int groups, size_t numel,
                                     const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ g,
-                                    float* __restrict__ dot, int taps, int cs, int ct, int coff, int dot_rows) {
+                                    float* __restrict__ dot, int taps, int cs, int ct, int coff, int dot_rows, size_t slab_stride) {
+    // STRIDED (behind wgrad_group_sum_kernel): consecutive slabs lie slab_stride floats apart - numel times the group's slab count,
+    // with nsplit == groups, one pre-summed slab per group.  Otherwise numel, and the code is the one it was (one more scalar in
+    // the <32> instantiation spills)
+    const size_t slab = STRIDED ? slab_stride : numel;
     __shared__ float red[MAXG][4];
     const int spg = nsplit / groups;
     const size_t rowlen = (size_t)taps * cs;
@@ -514,7 +518,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_reduce_kernel(const float* __res
             for (int q = 0; q < MAXG; ++q) {
                 if (q < groups) {
                     f32x4 s = zero;
-                    for (int k = 0; k < spg; ++k) s += *reinterpret_cast<const f32x4*>(partial + (size_t)(q * spg + k) * numel + i);
+                    for (int k = 0; k < spg; ++k) s += *reinterpret_cast<const f32x4*>(partial + (size_t)(q * spg + k) * slab + i);
                     const float sq = scale ? scale[q] : 1.f;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {  // the element order of the scalar path: bit-identical sums per element
@@ -539,7 +543,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_reduce_kernel(const float* __res
         for (int q = 0; q < MAXG; ++q) {
             if (q < groups) {
                 float s = 0.f;
-                for (int k = 0; k < spg; ++k) s += partial[(size_t)(q * spg + k) * numel + i];
+                for (int k = 0; k < spg; ++k) s += partial[(size_t)(q * spg + k) * slab + i];
                 tot = fmaf(s, scale ? scale[q] : 1.f, tot);
                 d[q] = fmaf(s, wi, d[q]);
             }
@@ -563,6 +567,29 @@ __global__ __launch_bounds__(256, 2) void wgrad_reduce_kernel(const float* __res
             else atomicAdd(dot + threadIdx.x, v);
         }
     }
+}
+
+// Narrow weights (a few thousand elements, many slabs per group): wgrad_reduce_kernel's grid comes from numel alone - one to a few
+// dozen workgroups, each lane walking the slabs of ALL its groups one load behind the other while the rest of the chip waits.  This
+// kernel takes the slab walk off that launch: wave (b, q) sums 64 quads of group q's spg slabs IN PLACE into the group's slab 0
+// (the partial sums are dead behind the reduce).  A lane adds its quad's slabs 0, 1, 2, ... one after the other onto zero - the order
+// and the operations of wgrad_reduce_kernel's own walk, so the sums are the same bits - with eight loads in flight instead of one.
+// wgrad_reduce_kernel then runs over one slab per group (its STRIDED instantiation; 0 + s == s) with its arithmetic unchanged.
+__global__ __launch_bounds__(64) void wgrad_group_sum_kernel(float* __restrict__ partial, int spg, size_t numel) {
+    const size_t i4 = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (i4 >= (numel >> 2)) return;
+    float* base = partial + (size_t)blockIdx.y * spg * numel + (i4 << 2);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    int k = 0;
+    for (; k + 8 <= spg; k += 8) {
+        f32x4 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = *reinterpret_cast<const f32x4*>(base + (size_t)(k + r) * numel);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s += v[r];
+    }
+    for (; k < spg; ++k) s += *reinterpret_cast<const f32x4*>(base + (size_t)k * numel);
+    *reinterpret_cast<f32x4*>(base) = s;
 }
 
 // dot[q] += sum over workgroup rows b of dot[(1 + b) * groups + q] in a FIXED order: eight lanes per group take rows b = lane (mod 8)
@@ -611,6 +638,73 @@ __global__ void sn_wgrad_finalize_kernel(const float* __restrict__ g, float* __r
             }
         }
         gw[i] = accumulate ? gw[i] + val : val;
+    }
+}
+
+// The same sums, bit for bit, without the strided gathers: sn_wgrad_finalize_kernel reads v[q][ci][t] with lanes along ci (a stride
+// of `taps` floats) and recomputes the coefficient of (q, co) for every element, `groups` times two dependent loads per element.  Here
+// a workgroup owns FIN_CO output channels x up to 256 weights of a run of input channels with all their taps - a contiguous piece of
+// v's own order.  Per chunk of FIN_Q groups it stages the coefficients -dot[q] * is * is * u[q][co] (the scalar expression's
+// operations in its order, once per (q, co)) and the piece of v (contiguous reads) in LDS; a thread keeps one weight position for its
+// FIN_CO channels in registers and reads v through the (t, ci) permutation on the LDS side (odd tap counts: no bank conflicts).  The
+// q loop of an element runs 0 .. groups - 1 as before.
+constexpr int FIN_CO = 8, FIN_Q = 16;
+__global__ __launch_bounds__(256) void sn_wgrad_finalize_tiled_kernel(const float* __restrict__ g, float* __restrict__ gw,
+                                                                      const float* __restrict__ dot, const float* __restrict__ inv_sigma,
+                                                                      const float* __restrict__ u, const float* __restrict__ v, int Cout,
+                                                                      int Cin, int taps, int groups, int accumulate, int ci_tile, int probe) {
+    if (probe) return;  // (dgmr_debug_flags 4096: the dispatch probe - a launch of THIS kernel leaves gw as it was)
+    __shared__ float sv[FIN_Q][256];
+    __shared__ __attribute__((aligned(16))) float sc[FIN_Q][FIN_CO];
+    const int tid = threadIdx.x;
+    const size_t K = (size_t)Cin * taps;
+    const int ci0 = (int)blockIdx.x * ci_tile, cit = min(ci_tile, Cin - ci0), nk = cit * taps;  // nk <= 256
+    const int co0 = (int)blockIdx.y * FIN_CO;
+    const bool ok = tid < nk;
+    const int t = ok ? tid / cit : 0, cil = ok ? tid - t * cit : 0;
+    const int vl = cil * taps + t;                 // this thread's weight position inside the staged piece of v
+    const size_t k = (size_t)t * Cin + ci0 + cil;  // ... and inside a row of g / gw
+    float val[FIN_CO];
+#pragma unroll
+    for (int c = 0; c < FIN_CO; ++c) val[c] = (ok && co0 + c < Cout) ? g[(size_t)(co0 + c) * K + k] : 0.f;
+    for (int q0 = 0; q0 < groups; q0 += FIN_Q) {
+        const int nq = min(FIN_Q, groups - q0);
+        if (tid < FIN_Q * FIN_CO) {
+            const int ql = tid / FIN_CO, c = tid - ql * FIN_CO;
+            float coef = 0.f;
+            if (ql < nq && co0 + c < Cout) {
+                const int q = q0 + ql;
+                const float is = inv_sigma[q];
+                coef = -dot[q] * is * is * u[(size_t)q * Cout + co0 + c];
+            }
+            sc[ql][c] = coef;
+        }
+        if (ok) {
+#pragma unroll 4
+            for (int ql = 0; ql < nq; ++ql) sv[ql][tid] = v[(size_t)(q0 + ql) * K + (size_t)ci0 * taps + tid];
+        }
+        __syncthreads();
+        if (ok) {
+            for (int ql = 0; ql < nq; ++ql) {
+                const float vv = sv[ql][vl];
+                const f32x4 c0 = *reinterpret_cast<const f32x4*>(&sc[ql][0]), c1 = *reinterpret_cast<const f32x4*>(&sc[ql][4]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    val[c] = fmaf(c0[c], vv, val[c]);
+                    val[4 + c] = fmaf(c1[c], vv, val[4 + c]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (ok) {
+#pragma unroll
+        for (int c = 0; c < FIN_CO; ++c) {
+            if (co0 + c < Cout) {
+                const size_t i = (size_t)(co0 + c) * K + k;
+                gw[i] = accumulate ? gw[i] + val[c] : val[c];
+            }
+        }
     }
 }
 
@@ -789,11 +883,20 @@ static const bool g_conv1x1 = []() {
     const char* e = getenv("DGMR_CONV1X1");
     return !(e && e[0] == '0');
 }();
+// DGMR_CONV1X1_STATS=1 (dgmr_debug_flags 512 inside a process): that kernel also writes the BatchNorm partial sums of its output
+// from its epilogue (stats_out) and dgmr_conv_stats_rows answers for it.  OFF by default: fp32 per-tile partial sums are another
+// rounding of the batch statistics than the separate pass's double sums from the first element, and on the benchmark's step that
+// rounding does not stay one; off, the BatchNorm behind the conv reads its input once more, as before
+static const bool g_conv1x1_stats_env = []() {
+    const char* e = getenv("DGMR_CONV1X1_STATS");
+    return e && e[0] == '1';
+}();
+static inline bool conv1x1_stats_on() { return g_conv1x1_stats_env || (g_debug_flags & 512); }
 static bool conv1x1_ok(const dgmr_conv_args& p, int64_t Mp) {  // Mp: pixels of the planned batch
     return g_conv1x1 && g_tune_variant < 0 && (g_precision == 1 || g_precision == 2) && p.w_split && p.KD == 1 && p.KH == 1 && p.KW == 1 &&
            p.Cin % 8 == 0 && p.Cin >= 32 && p.Cout % 4 == 0 && p.w_cin == p.Cin && p.w_coff == 0 && p.epi_mode == DGMR_EPI_PLAIN && !p.upsample &&
-           !p.pool2 && !p.pre_a && !p.addend && !p.residual && !p.mask_src && !p.stats_out && (p.reserved1 & 4) && al16(p.x) &&
-           ((int64_t)p.D * p.H * p.W) % 256 == 0 && Mp / 256 >= 512;  // (enough workgroups to fill the chip twice; tiles inside one sample)
+           !p.pool2 && !p.pre_a && !p.addend && !p.residual && !p.mask_src && (!p.stats_out || conv1x1_stats_on()) && (p.reserved1 & 4) &&
+           al16(p.x) && ((int64_t)p.D * p.H * p.W) % 256 == 0 && Mp / 256 >= 512;  // (enough workgroups to fill the chip twice; tiles inside one sample)
 }
 static bool stem4_ok(const dgmr_conv_args& p) {
     return g_stem4 && g_tune_variant < 0 && p.Cin == 4 && p.w_cin == 4 && p.w_coff == 0 && p.KH == 3 && p.KW == 3 &&
@@ -835,6 +938,10 @@ extern "C" int dgmr_conv_stats_rows(const dgmr_conv_args* a) {
     if (!a || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cout <= 0 || a->epi_mode != DGMR_EPI_PLAIN) return 0;
     dgmr_conv_args p = *a;
     conv_args_defaults(p);
+    // the streaming 1x1 kernel: one row per 256-pixel tile (tiles lie inside one sample, so the rows divide by BatchNorm groups); the
+    // same predicate, in the same place, as conv_dispatch - a conv it does not take keeps its separate statistics pass
+    const int64_t M64 = (int64_t)p.N * p.D * p.H * p.W;
+    if (!stem4_ok(p) && conv1x1_ok(p, M64 * (plan_n_of(p) / p.N))) return conv1x1_stats_on() && M64 < (1ll << 31) ? (int)(M64 / 256) : 0;
     WinPlan w;
     if (phase_plan(p, &w)) return 4 * w.grid_x;
     if (p.pool2) return pooled_plan(p, &w) ? w.grid_x : 0;
@@ -1258,6 +1365,45 @@ extern "C" int dgmr_conv_wgrad(const dgmr_wgrad_args* a, void* stream) {
 
 extern "C" int dgmr_wgrad_dot_floats(int groups) { return g_deterministic ? std::max(groups, 1) * (1 + 1024) : std::max(groups, 1); }
 
+// DGMR_WGRAD_NARROW=0: A/B switch for the two-stage reduce of narrow weight gradients (off: one launch of wgrad_reduce_kernel, as before)
+// (dgmr_debug_flags 1024: the same switch inside a process)
+static const bool g_wgrad_narrow = []() {
+    const char* e = getenv("DGMR_WGRAD_NARROW");
+    return !(e && e[0] == '0');
+}();
+// Narrow reduces use the whole chip: where wgrad_reduce_kernel would get at most WG_NARROW_BLOCKS workgroups (numel <= 8192: the 4 x 48
+// weight of the sampler's output layer with its 108 call groups, the discriminators' first convs, the latent stack) and a group has
+// at least WG_NARROW_SPG slabs to walk, the groups' slab sums are taken first by wgrad_group_sum_kernel, in place.  Returns the slab
+// stride for wgrad_reduce_kernel and rewrites *nsplit to one slab per group; 1 and nothing launched where the reduce stays as it was
+// (every launch with more workgroups).  A group's slabs are added in the single launch's order, so both paths give the same bits.
+constexpr int WG_NARROW_BLOCKS = 32, WG_NARROW_SPG = 4;
+static int wgrad_group_sums(const float* partial, int* nsplit, int groups, int64_t numel, hipStream_t s) {
+    const int spg = *nsplit / groups;
+    if (!g_wgrad_narrow || (g_debug_flags & 1024) || (numel + 255) / 256 > WG_NARROW_BLOCKS || spg < WG_NARROW_SPG || (numel & 3) || !al16(partial)) return 1;
+    hipLaunchKernelGGL(wgrad_group_sum_kernel, dim3((unsigned)((numel / 4 + 63) / 64), (unsigned)groups), dim3(64), 0, s,
+                       const_cast<float*>(partial), spg, (size_t)numel);
+    *nsplit = groups;
+    return spg;
+}
+
+static void launch_wgrad_reduce(int blocks, hipStream_t s, const float* partial, int nsplit, int groups, size_t numel, const float* w,
+                                const float* scale, float* g, float* dot, int taps, int cs, int ct, int coff, int sstride) {
+    const int rows = (dot && g_deterministic) ? 1 : 0;
+    const size_t slab = (size_t)sstride * numel;
+    const dim3 grid(blocks), wg(256);
+    if (sstride == 1 && groups <= 32)
+        hipLaunchKernelGGL(wgrad_reduce_kernel<32>, grid, wg, 0, s, partial, nsplit, groups, numel, w, scale, g, dot, taps, cs, ct, coff, rows, slab);
+    else if (sstride == 1)
+        hipLaunchKernelGGL(wgrad_reduce_kernel<WG_MAX_GROUPS>, grid, wg, 0, s, partial, nsplit, groups, numel, w, scale, g, dot, taps, cs, ct,
+                           coff, rows, slab);
+    else if (groups <= 32)
+        hipLaunchKernelGGL((wgrad_reduce_kernel<32, true, true>), grid, wg, 0, s, partial, nsplit, groups, numel, w, scale, g, dot, taps, cs, ct,
+                           coff, rows, slab);
+    else
+        hipLaunchKernelGGL((wgrad_reduce_kernel<WG_MAX_GROUPS, true, true>), grid, wg, 0, s, partial, nsplit, groups, numel, w, scale, g, dot,
+                           taps, cs, ct, coff, rows, slab);
+}
+
 extern "C" int dgmr_wgrad_reduce(const float* partial, int nsplit, int groups, int64_t numel, const float* w, const float* scale,
                                  float* g, float* dot, void* stream) {
     DGMR_CHECK_ARG(partial && g && numel > 0 && nsplit >= 1, "dgmr_wgrad_reduce: bad args");
@@ -1266,12 +1412,8 @@ extern "C" int dgmr_wgrad_reduce(const float* partial, int nsplit, int groups, i
                    groups, WG_MAX_GROUPS, nsplit);
     DGMR_CHECK_ARG(!dot || w, "dgmr_wgrad_reduce: dot needs w");
     const int blocks = (int)std::min<int64_t>((numel + 255) / 256, 1024);
-    if (groups <= 32)
-        hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, partial, nsplit, groups,
-                           (size_t)numel, w, scale, g, dot, 1, 1, 1, 0, (dot && g_deterministic) ? 1 : 0);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel<WG_MAX_GROUPS>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, partial, nsplit, groups,
-                           (size_t)numel, w, scale, g, dot, 1, 1, 1, 0, (dot && g_deterministic) ? 1 : 0);
+    const int sstride = wgrad_group_sums(partial, &nsplit, groups, numel, (hipStream_t)stream);
+    launch_wgrad_reduce(blocks, (hipStream_t)stream, partial, nsplit, groups, (size_t)numel, w, scale, g, dot, 1, 1, 1, 0, sstride);
     if (dot && g_deterministic)
         hipLaunchKernelGGL(wgrad_dot_finish_kernel, dim3(1), dim3(8 * WG_MAX_GROUPS), 0, (hipStream_t)stream, dot, groups, blocks);
     DGMR_CHECK_LAUNCH();
@@ -1288,18 +1430,22 @@ extern "C" int dgmr_wgrad_reduce_slice(const float* partial, int nsplit, int gro
     DGMR_CHECK_ARG(!dot || w, "dgmr_wgrad_reduce_slice: dot needs w");
     const int64_t numel = (int64_t)Cout * taps * cin_slice;
     const int blocks = (int)std::min<int64_t>((numel + 255) / 256, 1024);
+    const int sstride = wgrad_group_sums(partial, &nsplit, groups, numel, (hipStream_t)stream);
     // cs == ct would short-circuit the index map: force the mapped path whenever this is a true slice
-    if (groups <= 32)
-        hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, partial, nsplit, groups,
-                           (size_t)numel, w, scale, g, dot, taps, cin_slice, cin_total, coff, (dot && g_deterministic) ? 1 : 0);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel<WG_MAX_GROUPS>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, partial, nsplit, groups,
-                           (size_t)numel, w, scale, g, dot, taps, cin_slice, cin_total, coff, (dot && g_deterministic) ? 1 : 0);
+    launch_wgrad_reduce(blocks, (hipStream_t)stream, partial, nsplit, groups, (size_t)numel, w, scale, g, dot, taps, cin_slice, cin_total, coff,
+                        sstride);
     if (dot && g_deterministic)
         hipLaunchKernelGGL(wgrad_dot_finish_kernel, dim3(1), dim3(8 * WG_MAX_GROUPS), 0, (hipStream_t)stream, dot, groups, blocks);
     DGMR_CHECK_LAUNCH();
     return 0;
 }
+
+// DGMR_SN_FINALIZE_TILED=0 (dgmr_debug_flags 2048 inside a process): A/B switch for the LDS-tiled spectral-norm finalize; off, and
+// for the plain accumulate (u == nullptr, which has no gathers), sn_wgrad_finalize_kernel as before - the results are the same bits
+static const bool g_sn_finalize_tiled = []() {
+    const char* e = getenv("DGMR_SN_FINALIZE_TILED");
+    return !(e && e[0] == '0');
+}();
 
 extern "C" int dgmr_sn_wgrad_finalize(const float* g, float* gw, float* dot, const float* inv_sigma, const float* u,
                                       const float* v, int Cout, int Cin, int taps, int groups, int accumulate, void* stream) {
@@ -1309,8 +1455,14 @@ extern "C" int dgmr_sn_wgrad_finalize(const float* g, float* gw, float* dot, con
     const size_t total = (size_t)Cout * Cin * taps;
     const int blocks = (int)std::min<size_t>((total + 255) / 256, 2048);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_wgrad_finalize_kernel, dim3(blocks), dim3(256), 0, s, g, gw, dot, inv_sigma, u, v, Cout, Cin, taps, groups,
-                       accumulate);
+    const int ci_tile = taps <= 256 ? std::min(Cin, 256 / taps) : 0;
+    const int64_t tiles_y = ((int64_t)Cout + FIN_CO - 1) / FIN_CO;
+    if (u && g_sn_finalize_tiled && !(g_debug_flags & 2048) && ci_tile > 0 && tiles_y <= 65535)
+        hipLaunchKernelGGL(sn_wgrad_finalize_tiled_kernel, dim3((unsigned)((Cin + ci_tile - 1) / ci_tile), (unsigned)tiles_y), dim3(256), 0,
+                           s, g, gw, dot, inv_sigma, u, v, Cout, Cin, taps, groups, accumulate, ci_tile, (g_debug_flags & 4096) ? 1 : 0);
+    else
+        hipLaunchKernelGGL(sn_wgrad_finalize_kernel, dim3(blocks), dim3(256), 0, s, g, gw, dot, inv_sigma, u, v, Cout, Cin, taps, groups,
+                           accumulate);
     if (dot) hipLaunchKernelGGL(zero_n_kernel, dim3(1), dim3(WG_MAX_GROUPS), 0, s, dot, groups);
     DGMR_CHECK_LAUNCH();
     return 0;
@@ -1409,7 +1561,10 @@ extern "C" int dgmr_conv_tune(int variant, int ksplit, int window, int wgrad_win
 }
 
 extern "C" int dgmr_debug_flags(int flags) {
-    DGMR_CHECK_ARG(flags >= 0 && flags <= 511 && !(flags & 4), "dgmr_debug_flags: %d", flags);  // (256: phase launches one workgroup per ROW parity - tests, A/B)
+    // (256: phase launches one workgroup per ROW parity; 512: the 1x1 kernel's statistics ON; 1024 / 2048: the two-stage narrow reduce
+    //  and the tiled finalize OFF, as by their environment switches - tests, A/B; 4096: the tiled finalize, where it is dispatched,
+    //  writes nothing - the tests' proof of which kernel ran)
+    DGMR_CHECK_ARG(flags >= 0 && flags <= 8191 && !(flags & 4), "dgmr_debug_flags: %d", flags);
     g_debug_flags = flags;
     return 0;
 }

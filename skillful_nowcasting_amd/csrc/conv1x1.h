@@ -10,14 +10,15 @@
 //     eight rows (128 contiguous bytes per row and chunk), splits them into bf16 planes and stores them with the window
 //     kernels' swizzle (conv_win_glds.h); the items of chunk c + 1 are in flight in registers while chunk c is multiplied;
 //   * the weights of chunk c + 1 arrive by LDS-DMA under the MFMAs of chunk c (two stages), as in the window kernels;
-//   * epilogue: the window kernels' 16-byte one (quad transposes, 1/sigma, bias, 16-byte stores).
+//   * epilogue: the window kernels' 16-byte one (quad transposes, 1/sigma, bias, 16-byte stores), with their per-tile BatchNorm
+//     partial sums of the output on request (stats_out).
 // A tile never straddles two samples (D * H * W % 256 == 0 is the library's condition), so 1/sigma is one scalar per workgroup.
 #pragma once
 #include "conv_win_glds.h"  // lds_dma16, dma_drain, mfma_blk, lds_swz, quad_transpose
 
 namespace {
 
-template <int BN, int NS>
+template <int BN, int NS, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const dgmr_conv_args p, const int M, const int rows_per_sample) {
     constexpr int CK = 32, ROW = CK / 2, BM = 256;
     constexpr int NP = planes_of<NS>::value;
@@ -168,26 +169,73 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const dgmr_conv_args p,
     }
 
     // ---- 16-byte epilogue (Cout % 4 == 0, aligned tensors: the library's condition) ----
+    // stats_out: BatchNorm statistics of the OUTPUT for the next layer, as in the window kernels - per column sum y and sum y^2 of the
+    // values stored (after scale, bias and relu; rows m < M only).  A lane holds the same four columns in all its rows (j4 and rsel
+    // pick the row), so it sums its eight rows per column block, the eight lanes of a column quad are folded by three exchanges, the
+    // four waves through LDS, and the workgroup writes its column range of ONE row [2][Cout] per 256-pixel tile.  Plain adds in an
+    // order that depends on indices only: two launches give the same bits.  STATS is a template parameter of the kernel: the
+    // instantiation without it is, instruction for instruction, the kernel it was.
     const float sc = p.scale ? p.scale[(m0 / rows_per_sample) / p.scale_group] : 1.f;
     const int j4 = lane & 3, q4 = (lane & 31) >> 2, rsel = lane >> 5;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    {
+        float* red = reinterpret_cast<float*>(smem);  // [4 waves][BN][2] (every wave is past the barrier behind the last chunk)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col4 = n0 + j * 32 + 4 * q4;
-        const bool cok = col4 < p.Cout;
-        const f32x4 b4 = (p.bias && cok) ? *reinterpret_cast<const f32x4*>(p.bias + col4) : zero4;
+        for (int j = 0; j < TN; ++j) {
+            const int col4 = n0 + j * 32 + 4 * q4;
+            const bool cok = col4 < p.Cout;
+            const f32x4 b4 = (p.bias && cok) ? *reinterpret_cast<const f32x4*>(p.bias + col4) : zero4;
+            float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
+            for (int i = 0; i < TM; ++i) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int m = m0 + wid * 64 + i * 32 + j4 + 8 * g + 4 * rsel;
-                f32x4 v = quad_transpose(acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], lane);
+                for (int g = 0; g < 4; ++g) {
+                    const int m = m0 + wid * 64 + i * 32 + j4 + 8 * g + 4 * rsel;
+                    f32x4 v = quad_transpose(acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], lane);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    v[c] = fmaf(v[c], sc, b4[c]);
-                    if (p.act_relu) v[c] = fmaxf(v[c], 0.f);
+                    for (int c = 0; c < 4; ++c) {
+                        v[c] = fmaf(v[c], sc, b4[c]);
+                        if (p.act_relu) v[c] = fmaxf(v[c], 0.f);
+                    }
+                    if (cok && m < M) *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + col4) = v;
+                    if constexpr (STATS) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const float o = m < M ? v[c] : 0.f;
+                            s0[c] += o;
+                            s1[c] = fmaf(o, o, s1[c]);
+                        }
+                    }
                 }
-                if (cok && m < M) *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + col4) = v;
+            }
+            if constexpr (STATS) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {  // the eight lanes of this column quad: j4 (lane bits 0, 1), then rsel (bit 5)
+                    s0[c] += __shfl_xor(s0[c], 1, 64);
+                    s1[c] += __shfl_xor(s1[c], 1, 64);
+                    s0[c] += __shfl_xor(s0[c], 2, 64);
+                    s1[c] += __shfl_xor(s1[c], 2, 64);
+                    s0[c] += __shfl_xor(s0[c], 32, 64);
+                    s1[c] += __shfl_xor(s1[c], 32, 64);
+                }
+                if (j4 == 0 && rsel == 0) {
+                    float* dst = red + (wid * BN + j * 32 + 4 * q4) * 2;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        dst[2 * c + 0] = s0[c];
+                        dst[2 * c + 1] = s1[c];
+                    }
+                }
+            }
+        }
+        if constexpr (STATS) {
+            __syncthreads();
+            for (int idx = tid; idx < BN * 2; idx += 256) {
+                const int cl = idx >> 1, which = idx & 1;
+                float v = 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v += red[(q * BN + cl) * 2 + which];
+                if (n0 + cl < p.Cout) p.stats_out[((size_t)blockIdx.x * 2 + which) * p.Cout + n0 + cl] = v;
             }
         }
     }

@@ -60,9 +60,10 @@ class Sampler(torch.nn.Module, PyTorchModelHubMixin):
             # the 1x1 conv, the G-block and the upsampling G-block (one launch per conv instead of T), every forecast step
             # keeping its own spectral-norm sigma and BatchNorm batch statistics exactly as the reference's T calls do
             h = gru.forward_batched(h, init_states[3 - lvl], T, x_shared=(lvl == 0), draws=draws, layout=lay)
-            h = c11(h, calls=calls, layout=lay)
             # BatchNorm batch statistics travel with the tensors: the conv that writes a BatchNorm's input sums it in its epilogue
-            h, st = g(h, calls=calls, layout=lay, out_stats=True)
+            # (the 1x1 conv too where the streaming kernel takes it and DGMR_CONV1X1_STATS is on; st is None otherwise and g.bn1 reads h)
+            h, st = c11(h, calls=calls, layout=lay, want_stats=True)
+            h, st = g(h, calls=calls, layout=lay, in_stats=st, out_stats=True)
             if lvl == 3:
                 h, st = upg(h, calls=calls, layout=lay, in_stats=st, out_stats=True)
             else:
