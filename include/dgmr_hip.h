@@ -584,6 +584,22 @@ int dgmr_crop_gather(const void* frames, int dtype, int T, int H, int W, int C, 
                      float scale, float offset, int clamp_missing, float missing_fill, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Tiled full-frame nowcasts (tiling.py: nowcast_tiled, DGMR.nowcast_full_frame).  New symbol, same ABI version.
+ * One tile's forecast pred [planes][tile][tile] is added, weighted, into the frame out [planes][H][W] (planes = K * T * C) at the
+ * tile's top-left corner (oy, ox).  For every (p, i, j):
+ *     out[p][oy + i][ox + j] = fmaf(wy[i] * wx[j], pred[p][i][j], out[p][oy + i][ox + j])
+ * with the product wy[i] * wx[j] rounded to fp32 FIRST (one fmul_rn, then one fma).  wy, wx: `tile` floats each, the separable
+ * blending weights of this tile (tiling.py: blend_weights; over the tiles that cover a pixel they sum to one).  Nothing outside
+ * the tile's rectangle is read or written, and there are no atomics: the launches of one nowcast go to one stream in raster order,
+ * so the sum at a pixel is formed in that order and two runs give the same bits.  Rows are moved in 16-byte pieces: tile, ox and W
+ * are multiples of 4 and pred, out, wx are 16-byte aligned.  Argument errors (null pointers, non-positive extents, tile / ox / W not
+ * multiples of 4, a misaligned pointer, a tile that is not inside the frame: oy < 0, oy + tile > H, ox < 0, ox + tile > W) return
+ * < 0 and set dgmr_last_error() before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_tile_blend(const float* pred, float* out, const float* wy, const float* wx, int64_t planes, int tile, int H, int W,
+                    int oy, int ox, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

@@ -153,6 +153,7 @@ SIGNATURES = {
     "dgmr_swap_multi": [P, P, i, i, P],
     "dgmr_crop_scores": [P, i, i, i, i, i, f, f, c_double, i, i, P, P, P, P, P],
     "dgmr_crop_gather": [P, i, i, i, i, i, P, i, i, f, f, i, f, P, P],
+    "dgmr_tile_blend": [P, P, P, P, L, i, i, i, i, i, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],

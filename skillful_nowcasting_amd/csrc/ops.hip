@@ -1387,6 +1387,45 @@ __global__ __launch_bounds__(64 * CROP_WAVES) void crop_gather_kernel(const T* _
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// tiled full-frame nowcasts (tiling.py: nowcast_tiled): one tile's forecast blended into the frame
+// ------------------------------------------------------------------------------------------------
+// Rows to waves like crop_gather_kernel, lanes along j in 16-byte pieces: a tile row is q = tile / 4 pieces and takes lpr = min(q, 64)
+// lanes, so a wave instruction covers 64 / lpr whole rows (one 1 KiB row of a 256-pixel tile; eight rows of a 32-pixel one) and every
+// row segment of `pred` and of `out` is read, and `out` written, as contiguous 16-byte pieces.  A lane's column never changes from
+// row to row: its piece of wx is loaded once per wave (tiles wider than 256 pixels reload the further pieces), wy[i] once per row.
+// pred is read once, the covered part of out read and written once; nothing else is touched.
+__global__ __launch_bounds__(64 * CROP_WAVES) void tile_blend_kernel(const f32x4* __restrict__ pred, float* __restrict__ out,
+                                                                     const float* __restrict__ wy, const f32x4* __restrict__ wx,
+                                                                     int rows, int tile, int H, int W, int oy, int ox) {
+    const int lane = threadIdx.x & 63;
+    const int q = tile >> 2, lpr = q < 64 ? q : 64, rpw = 64 / lpr;
+    const int sub = lane / lpr, jl = lane - sub * lpr;
+    if (sub >= rpw) return;  // (q does not divide 64: the last lanes of a wave have no row)
+    const int64_t step = (int64_t)gridDim.x * CROP_WAVES * rpw;
+    const f32x4 wx0 = wx[jl];
+    for (int64_t row64 = (int64_t)(blockIdx.x * CROP_WAVES + (threadIdx.x >> 6)) * rpw + sub; row64 < rows; row64 += step) {
+        const int row = (int)row64, p = row / tile, i = row - p * tile;
+        const float wyi = wy[i];
+        const f32x4* __restrict__ src = pred + (int64_t)row * q;
+        f32x4* __restrict__ dst = (f32x4*)(out + ((int64_t)p * H + oy + i) * W + ox);
+        f32x4 w = wx0;
+        for (int j = jl;;) {
+            const f32x4 v = src[j];
+            f32x4 o = dst[j];
+            // the weight is rounded to fp32 before the fma (dgmr_hip.h)
+            o.x = fmaf(__fmul_rn(wyi, w.x), v.x, o.x);
+            o.y = fmaf(__fmul_rn(wyi, w.y), v.y, o.y);
+            o.z = fmaf(__fmul_rn(wyi, w.z), v.z, o.z);
+            o.w = fmaf(__fmul_rn(wyi, w.w), v.w, o.w);
+            dst[j] = o;
+            j += lpr;
+            if (j >= q) break;
+            w = wx[j];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int dgmr_spectral_sigma(const float* w, float* u, float* v, float* u_save, float* v_save, float* inv_sigma,
@@ -2212,6 +2251,27 @@ extern "C" int dgmr_crop_gather(const void* frames, int dtype, int T, int H, int
         default: CROP_GATHER(float); break;
     }
 #undef CROP_GATHER
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_tile_blend(const float* pred, float* out, const float* wy, const float* wx, int64_t planes, int tile, int H, int W,
+                               int oy, int ox, void* stream) {
+    DGMR_CHECK_ARG(pred && out && wy && wx, "dgmr_tile_blend: null pointer");
+    DGMR_CHECK_ARG(planes > 0 && tile > 0 && H > 0 && W > 0, "dgmr_tile_blend: planes=%lld tile=%d H=%d W=%d must be positive",
+                   (long long)planes, tile, H, W);
+    DGMR_CHECK_ARG(tile % 4 == 0 && ox % 4 == 0 && W % 4 == 0, "dgmr_tile_blend: tile=%d, ox=%d and W=%d must be multiples of 4", tile,
+                   ox, W);
+    DGMR_CHECK_ARG(oy >= 0 && ox >= 0 && (int64_t)oy + tile <= H && (int64_t)ox + tile <= W,
+                   "dgmr_tile_blend: tile %d at (oy=%d, ox=%d) is not inside the frame %d x %d", tile, oy, ox, H, W);
+    DGMR_CHECK_ARG((((uintptr_t)pred | (uintptr_t)out | (uintptr_t)wx) & 15) == 0, "dgmr_tile_blend: pred, out and wx must be 16-byte aligned");
+    DGMR_CHECK_ARG(planes <= INT64_MAX / ((int64_t)H * W), "dgmr_tile_blend: planes=%lld x %d x %d out of range", (long long)planes, H, W);
+    DGMR_CHECK_ARG(planes <= INT32_MAX / tile, "dgmr_tile_blend: planes=%lld x tile=%d rows out of range", (long long)planes, tile);
+    const int rows = (int)(planes * tile);
+    const int q = tile / 4, rpw = 64 / (q < 64 ? q : 64);
+    const int blocks = std::min(cdiv(cdiv(rows, rpw), CROP_WAVES), 256 * 8);
+    hipLaunchKernelGGL(tile_blend_kernel, dim3(blocks), dim3(64 * CROP_WAVES), 0, ST, (const f32x4*)pred, out, wy, (const f32x4*)wx, rows,
+                       tile, H, W, oy, ox);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

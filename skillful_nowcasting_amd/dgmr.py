@@ -404,6 +404,60 @@ class DGMR(
         out = self._generate(images.float(), k, grad=False)
         return out.view(k, images.shape[0], *out.shape[1:])
 
+    def nowcast_full_frame(self, frames, num_samples: int = None, tile: int = None, stride: int = None, scale: float = 1.0,
+                           offset: float = 0.0, clamp_missing: bool = True, missing_fill: float = 0.0, use_ema: bool = False,
+                           generator=None, zs=None, out=None):
+        """Ensemble nowcast of a whole frame larger than the model: `num_samples` forecasts -> fp32 [num_samples, forecast_steps, C,
+        H, W] (tiling.py; INTEGRATION.md "Nowcasting a full frame").
+
+        frames: one sequence [T_in >= 4, H, W, C] on the model's device in its storage dtype (uint8 / int16 / float16 / float32; the
+        last 4 frames are the context), H and W multiples of 32; `scale`, `offset`, `clamp_missing`, `missing_fill`: the affine to
+        the physical value and the treatment of missing elements, as in `data.gather_crops`.  The generator runs on overlapping
+        `tile`-sized tiles (default: the model's output_shape) `stride` pixels apart (default: tile - 64, a 64-pixel overlap; tile
+        itself where tile <= 64), one tile per `forward_draws` call with all draws, and the tile forecasts are blended with weights
+        that sum to one at every pixel.  Each ensemble member has one latent map for the whole frame - `zs` [num_samples, 8 * C,
+        H // 32, W // 32], or drawn here on the CPU from `generator` (a seeded torch.Generator reproduces a nowcast) - and every
+        tile reads its part of it.  Eval mode only: train-mode BatchNorm would normalise every tile by its own statistics and move
+        the running ones.  No model state moves.  use_ema: nowcast from the averaged generator (inside ema_scope())."""
+        from . import tiling
+
+        if self.training:
+            raise RuntimeError("nowcast_full_frame in training mode: BatchNorm would use per-tile batch statistics and every tile "
+                               "would advance the model's buffers; call model.eval() first")
+        if use_ema:
+            with self.ema_scope():
+                return self.nowcast_full_frame(frames, num_samples, tile, stride, scale, offset, clamp_missing, missing_fill, False,
+                                               generator, zs, out)
+        if frames.dim() != 4:
+            raise ValueError(f"frames must be [T, H, W, C], got shape {tuple(frames.shape)}")
+        if frames.shape[0] < 4:
+            raise ValueError(f"frames holds {frames.shape[0]} frames, the context needs 4")
+        t_out = self.sampler.forecast_steps
+        h, w, c = (int(v) for v in frames.shape[1:])
+        if c != self.input_channels:
+            raise ValueError(f"frames has {c} channels, the model {self.input_channels}")
+        tile = int(self.latent_stack.shape[1]) * tiling.LATTICE if tile is None else tile
+        stride = (tile - 64 if tile > 64 else tile) if stride is None else stride
+        tiling.tile_origins(h, tile, stride), tiling.tile_origins(w, tile, stride)  # (refuses a bad geometry before anything is drawn)
+        if zs is None:
+            k = self.num_samples if num_samples is None else int(num_samples)
+            zs = ops.upload(tiling.latent_field(k, 8 * self.input_channels, h // tiling.LATTICE, w // tiling.LATTICE, generator),
+                            frames.device, torch.float32)
+        else:
+            want = (8 * self.input_channels, h // tiling.LATTICE, w // tiling.LATTICE)
+            if not isinstance(zs, torch.Tensor) or zs.dim() != 4 or tuple(zs.shape[1:]) != want or zs.dtype != torch.float32:
+                raise ValueError(f"zs must be a float32 [num_samples, {want[0]}, {want[1]}, {want[2]}] tensor, got "
+                                 f"{tuple(zs.shape) if isinstance(zs, torch.Tensor) else type(zs).__name__}")
+            if num_samples is not None and zs.shape[0] != num_samples:
+                raise ValueError(f"zs holds {zs.shape[0]} latent maps for num_samples={num_samples}")
+        device = next(self.generator.parameters()).device
+        if frames.device != device or zs.device != device:
+            raise ValueError(f"frames ({frames.device}) and zs ({zs.device}) must be on the model's device {device}")
+        k = int(zs.shape[0])
+        with torch.no_grad():
+            return tiling.nowcast_tiled(lambda context, z: self.generator.forward_draws(context, k, zs=z), frames[-4:], zs, tile, stride,
+                                        t_out, scale, offset, clamp_missing, missing_fill, out)
+
     def attach_data_parallel(self, process_group=None, chunk_mb: int = 64, overlap: bool = True, force_exchange: bool = False):
         """One-process-per-GPU data parallelism: flat gradient buffers, RCCL all-reduce of 64 MB buckets launched while the backward
         pass is still running (`overlap`), buffers broadcast from rank 0 once per step."""
