@@ -600,6 +600,34 @@ int dgmr_tile_blend(const float* pred, float* out, const float* wy, const float*
                     int oy, int ox, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ensemble verification (verification.py: ensemble_scores, NowcastVerifier).  New symbols, same ABI version.
+ * forecast: M members of N planes [H][W], fp32; member m starts at forecast + m * member_stride (elements), its planes are
+ * contiguous ([N][H][W]).  observed: [N][H][W] fp32 in the same unit; an observed element is MISSING when !(y >= 0.f) (negative,
+ * -inf, NaN: the loader's rule); forecast values are taken as they are.  scales: S distinct values out of {1, 2, 4, 8, 16} (HOST
+ * array, read during the call); thresholds: K <= 8 floats on the DEVICE.  Per plane n, with a cell of scale s being one of the
+ * non-overlapping s x s blocks (stride s) whose s * s observed elements are all present, x_m / y its pooled member / observation
+ * (pool 0: the float64 sum of the s * s fp32 values / (s * s), formed as (top-left + top-right) + (bottom-left + bottom-right) level by
+ * level; pool 1: the maximum):
+ *   cells[n][si]              int64   number of cells of scales[si]
+ *   abs_err[n][pool][si]      double  sum over cells of (1 / M) sum_m |x_m - y|
+ *   pair[n][pool][si]         double  sum over cells of sum_{m<k} |x_m - x_k|      (at scale 1 the two pool rows are the same bits)
+ *   contingency[n][k][m][3]   int64   over present pixels: hits (x >= thr_k, y >= thr_k), misses (x < thr_k, y >= thr_k), false
+ *                                     alarms (x >= thr_k, y < thr_k); fp32 comparisons
+ *   ranks[n][b][e]            int64   present pixels with b = #{m: x_m < y} and e = #{m: x_m == y}; [M + 1][M + 1]
+ * Every element of forecast and observed is read once (16-byte loads: both pointers 16-byte aligned, member_stride % 4 == 0, H and W
+ * multiples of 16); besides the outputs only `workspace` is written: dgmr_ensemble_scores_workspace(M, N, H, W) bytes (8-byte aligned;
+ * < 0 for a shape the call would refuse) of per-workgroup float64 partials, which a second small launch adds in index order - no
+ * floating-point atomics, two calls give the same bits; the integer counts are added with integer atomics onto outputs the call
+ * clears first.  Runs on `stream`, does not synchronise.  Argument errors (null pointers, M outside 1 ... 32, H or W not a multiple of
+ * 16, a scale outside the set or given twice, K > 8, misaligned pointers or stride, a workspace that is too small) return < 0 and set
+ * dgmr_last_error() before anything is enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgmr_ensemble_scores_workspace(int M, int64_t N, int H, int W);
+int dgmr_ensemble_scores(const float* forecast, int64_t member_stride, const float* observed, int M, int64_t N, int H, int W,
+                         const int* scales, int S, const float* thresholds, int K, void* workspace, int64_t workspace_bytes,
+                         int64_t* cells, double* abs_err, double* pair, int64_t* contingency, int64_t* ranks, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

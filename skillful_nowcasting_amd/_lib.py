@@ -154,6 +154,7 @@ SIGNATURES = {
     "dgmr_crop_scores": [P, i, i, i, i, i, f, f, c_double, i, i, P, P, P, P, P],
     "dgmr_crop_gather": [P, i, i, i, i, i, P, i, i, f, f, i, f, P, P],
     "dgmr_tile_blend": [P, P, P, P, L, i, i, i, i, i, P],
+    "dgmr_ensemble_scores": [P, L, P, i, L, i, i, POINTER(c_int), i, P, i, P, L, P, P, P, P, P, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],
@@ -181,7 +182,8 @@ SIGNATURES = {
 }
 del i, f, L
 # buffer sizes: these return int64_t
-SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_grid_cell_acc_doubles": [c_int64]}
+SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_grid_cell_acc_doubles": [c_int64],
+                  "dgmr_ensemble_scores_workspace": [c_int, c_int64, c_int, c_int]}
 
 _lib = None
 

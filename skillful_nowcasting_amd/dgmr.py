@@ -458,6 +458,20 @@ class DGMR(
             return tiling.nowcast_tiled(lambda context, z: self.generator.forward_draws(context, k, zs=z), frames[-4:], zs, tile, stride,
                                         t_out, scale, offset, clamp_missing, missing_fill, out)
 
+    def verify_batch(self, batch, verifier, num_samples: int = None, use_ema: bool = False, weights=None):
+        """Draw an ensemble for `batch[0]` (`sample`) and score it against `batch[1]` into `verifier` (verification.NowcastVerifier:
+        pooled CRPS, CSI, rank table per lead time; INTEGRATION.md "Verifying ensemble nowcasts").  weights: one per case, the
+        paper's 1 / q for importance-sampled crops (`1.0 / loader.last_inclusion_prob`).  Eval mode only: the scores of train-mode
+        forwards (batch-statistics BatchNorm, moving buffers) say nothing about the nowcasts a user gets.  Returns the ensemble
+        [num_samples, B, T, C, H, W].  use_ema: draw from the averaged generator."""
+        if self.training:
+            raise RuntimeError("verify_batch in training mode: BatchNorm would use batch statistics and advance the model's buffers; "
+                               "call model.eval() first")
+        images, future_images = batch
+        out = self.sample(images, num_samples, use_ema)
+        verifier.update(out, future_images.float(), weights)
+        return out
+
     def attach_data_parallel(self, process_group=None, chunk_mb: int = 64, overlap: bool = True, force_exchange: bool = False):
         """One-process-per-GPU data parallelism: flat gradient buffers, RCCL all-reduce of 64 MB buckets launched while the backward
         pass is still running (`overlap`), buffers broadcast from rank 0 once per step."""
