@@ -628,6 +628,44 @@ int dgmr_ensemble_scores(const float* forecast, int64_t member_stride, const flo
                          int64_t* cells, double* abs_err, double* pair, int64_t* contingency, int64_t* ranks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Radially averaged power spectral density (spectra.py: radial_psd, SpectrumVerifier).  New symbols, same ABI version.
+ * x: N planes [H][W] of fp32, plane n at x + n * plane_stride (elements; >= H * W, a multiple of 4), rows contiguous, x 16-byte
+ * aligned.  A plane is cut into (H / L) x (W / L) non-overlapping L x L windows, L one of 32, 64, 128, 256, 512; windows are numbered
+ * row-major over [N][H / L][W / L].  Per window: an element is MISSING when !(x >= 0.f) (the loader's rule), is read as 0 and counted
+ * in missing[window]; F = fft2(window), unnormalised, NO window function and NO detrending; with integer frequencies kx, ky in
+ * {-L/2 ... L/2 - 1} a mode belongs to bin r = round(sqrt(kx^2 + ky^2)), found in integers (r (r - 1) < kx^2 + ky^2 <= r (r + 1));
+ *   power[window][r]  double  sum of |F|^2 over the modes of bin r, r = 0 ... L / 2 - 1 (modes with r >= L / 2 - the corners, the
+ *                             Nyquist row and column - are dropped).  Sums, not means: the mode counts depend on L alone.
+ * fp32 transforms (radix 2, twiddles from a table computed in double), |F|^2 formed in fp32 and added in float64; the input's
+ * Hermitian symmetry is used (half spectrum, kx > 0 counted twice).  L <= 128: one workgroup per window, everything in LDS.  L >= 256:
+ * a row pass writes the transposed half spectrum of a round of windows to the workspace, a column pass transforms and bins it, a
+ * small launch adds the column workgroups' bin partials in index order.  workspace (16-byte aligned): a 2 KiB twiddle table plus,
+ * for L >= 256, 4 L^2 + 8 (L / 2) (L / 2 / c) bytes per window of a round (c = 32 columns per workgroup at 256, 16 at 512).
+ * dgmr_radial_psd_workspace returns what the whole call would use, capped at 64 MiB (+ the table; < 0 for a shape the call would
+ * refuse); any workspace of at least dgmr_radial_psd_workspace(1, L, L, L) bytes is accepted and only sets how many windows a round
+ * takes - the results are the same bits for every workspace size, and two calls give the same bits (no floating-point atomics).
+ * Runs on `stream`, does not synchronise.  Argument errors (null pointers, L outside the set, H or W not a multiple of L, N < 1,
+ * misaligned pointer or stride, a workspace below the one-window need) return < 0 and set dgmr_last_error() before anything is
+ * enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgmr_radial_psd_workspace(int64_t N, int H, int W, int L);
+int dgmr_radial_psd(const float* x, int64_t plane_stride, int64_t N, int H, int W, int L, void* workspace, int64_t workspace_bytes,
+                    double* power, int64_t* missing, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Exceedance table (value.py: exceedance_table, ValueVerifier).  New symbol, same ABI version.
+ * forecast, member_stride, observed, M, N, H, W, thresholds, K: as in dgmr_ensemble_scores, with the same missing rule, fp32
+ * comparisons, alignment rules and refusals (1 <= M <= 32, H and W multiples of 16, K <= 8 thresholds on the DEVICE).
+ *   table[n][k][j][o]  int64  present pixels of plane n at which exactly j of the M members are >= thr_k and the observation is
+ *                             (o = 1) or is not (o = 0) >= thr_k; [N][K][M + 1][2]
+ * One streaming read of the ensemble and the observation (16-byte loads), a per-workgroup integer histogram in LDS, integer atomics
+ * onto a table the call clears first: exact, independent of the order, no workspace.  K = 0 enqueues nothing.  Runs on `stream`,
+ * does not synchronise.  Argument errors return < 0 and set dgmr_last_error() before anything is enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_exceedance_table(const float* forecast, int64_t member_stride, const float* observed, int M, int64_t N, int H, int W,
+                          const float* thresholds, int K, int64_t* table, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

@@ -155,6 +155,8 @@ SIGNATURES = {
     "dgmr_crop_gather": [P, i, i, i, i, i, P, i, i, f, f, i, f, P, P],
     "dgmr_tile_blend": [P, P, P, P, L, i, i, i, i, i, P],
     "dgmr_ensemble_scores": [P, L, P, i, L, i, i, POINTER(c_int), i, P, i, P, L, P, P, P, P, P, P],
+    "dgmr_radial_psd": [P, L, L, i, i, i, P, L, P, P, P],
+    "dgmr_exceedance_table": [P, L, P, i, L, i, i, P, i, P, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],
@@ -183,7 +185,8 @@ SIGNATURES = {
 del i, f, L
 # buffer sizes: these return int64_t
 SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_grid_cell_acc_doubles": [c_int64],
-                  "dgmr_ensemble_scores_workspace": [c_int, c_int64, c_int, c_int]}
+                  "dgmr_ensemble_scores_workspace": [c_int, c_int64, c_int, c_int],
+                  "dgmr_radial_psd_workspace": [c_int64, c_int, c_int, c_int]}
 
 _lib = None
 

@@ -128,7 +128,7 @@ def ensemble_scores_reference(forecast, observed, scales: Sequence[int] = DEFAUL
 
 # ---- the device path -------------------------------------------------------------------------------------------------------------
 # Both caches live as long as the process and never shrink: one workspace per (device, stream) that ever called - its largest size so
-# far, a few hundred KB - and one tensor of at most 8 floats per (device, distinct thresholds).  A process uses a handful of either.
+# far, a few hundred KB for the scores (spectra.radial_psd shares it: up to 64 MiB with 256- or 512-pixel windows) - and one tensor of at most 8 floats per (device, distinct thresholds).  A process uses a handful of either.
 _WORKSPACES = {}  # (device index, stream) -> uint8 tensor; a launch sequence owns it until the stream has run it
 _THRESHOLDS = {}  # (device index, threshold bytes) -> (device tensor, upload event, stream of the upload)
 
