@@ -666,6 +666,42 @@ int dgmr_exceedance_table(const float* forecast, int64_t member_stride, const fl
                           const float* thresholds, int K, int64_t* table, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The advection baseline (advection.py; csrc/advect.hip).  New symbols, same ABI version.
+ *
+ * Block matching (TREC) between two frames.  prev, next: N fp32 planes of H x W, plane_stride elements apart; an element with
+ * !(x >= 0) is missing and read as 0.  Blocks of block x block pixels with their top-left corners at (by stride, bx stride) on the
+ * lattice By = (H - block) / stride + 1 by Bx = (W - block) / stride + 1; what of `next` lies beyond the last block is never read.
+ *   wet[n][by][bx]      int32  elements of the `next` block (missing ones as 0) that are >= wet_threshold, compared in fp32
+ *   disp[n][by][bx][2]  int32  (dy, dx), |dy|, |dx| <= radius: the candidate of least cost.  d is a candidate when the displaced block
+ *                              prev[y0 - dy ...][x0 - dx ...] lies wholly inside the H x W frame; its cost is the sum over the block
+ *                              of (next[y0 + i][x0 + j] - prev[y0 - dy + i][x0 - dx + j])^2, fp32, fmaf in row-major pixel order by
+ *                              one thread.  Ties: the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx.
+ *   cost[n][by][bx][5]  fp32   the minimum, then the costs at (dy - 1, dx), (dy + 1, dx), (dy, dx - 1), (dy, dx + 1); +inf where that
+ *                              neighbour is no candidate
+ * A block with wet < min_wet is dry: no search, disp = (0, 0), all five costs +inf.  One workgroup per (plane, block), the block and
+ * the (block + 2 radius)^2 window of `prev` staged in LDS once; two launches give the same bits.  Supported: block 16 or 32,
+ * 1 <= stride <= block, 1 <= radius <= 16, H, W >= block, N >= 1, min_wet >= 0; everything else and null pointers return < 0 and set
+ * the error message before anything is enqueued.  No alignment demands.  Runs on `stream`, does not synchronise.
+ *
+ * Semi-Lagrangian extrapolation of x (N planes of H x W, x_plane_stride apart; missing elements read as 0) along a motion field for
+ * T lead times in one launch.  field[n][gy][gx][2] = (vy, vx) in pixels per step at pixel (origin + gy spacing, origin + gx spacing),
+ * field_plane_stride elements per plane (0: one field for all planes).  v(p): bilinear interpolation of the lattice, positions
+ * clamped to its extent (Gy = Gx = 1: a uniform field).  s(p): bilinear interpolation of x, a tap outside the frame is 0.
+ *   D_0 = 0;  D_t(p) = D_(t-1)(p) + v(p - D_(t-1)(p));  out[n][t - 1][p] = s(p - D_t(p)),  t = 1 ... T,
+ * written to out + n out_plane_stride + (t - 1) out_step_stride + y W + x: every lead time interpolates the source once.  Every
+ * interpolation is a + f (b - a) with one fma, so an integer displacement copies the source bit for bit.  Against exact arithmetic
+ * the result is within  c T max(H, W) 2^-24 A + 4 * 2^-24 max|x|,  A the largest difference of adjacent elements of x, c = 22 the
+ * rounded fp32 operations per step in the position arithmetic of both axes (advect.hip lists them), for fields that change by less
+ * than 1 / (4 T) pixels per pixel and displacements that stay below max(H, W).  1 <= T <= 64, spacing > 0, Gy, Gx >= 1; 16-byte
+ * stores are used when W, out and its two strides allow them and 4-byte stores otherwise: no alignment demands.  Argument errors
+ * return < 0 and set the error message before anything is enqueued.  Runs on `stream`, does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_block_match(const float* prev, const float* next, int64_t plane_stride, int64_t N, int H, int W, int block, int stride, int radius,
+                     float wet_threshold, int min_wet, int32_t* disp, float* cost, int32_t* wet, void* stream);
+int dgmr_advect(const float* x, int64_t x_plane_stride, const float* field, int64_t field_plane_stride, int64_t N, int H, int W, int Gy,
+                int Gx, float origin, float spacing, int T, float* out, int64_t out_plane_stride, int64_t out_step_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

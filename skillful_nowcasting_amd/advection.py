@@ -1,0 +1,394 @@
+"""The advection baseline: block-matching motion (TREC), semi-Lagrangian extrapolation, Eulerian persistence (what the
+paper plots DGMR against; INTEGRATION.md "A baseline to beat").
+
+  * `block_match`: per block of `next`, the integer displacement (dy, dx) of least squared difference against `prev` - the echo
+    moved by +d between the two frames - with the costs of its four neighbours and the block's wet count;
+  * `motion_field`: block matching over consecutive context frames, a parabola through the neighbour costs for the sub-pixel part,
+    the pairs averaged, the lattice smoothed and filled;
+  * `advect`: the last frame extrapolated along the field for all lead times, each lead time interpolating the source once;
+  * `AdvectionNowcaster`, `persistence_nowcast`: forecasts in the layout of `DGMR.nowcast_full_frame` / `DGMR.sample` with one member,
+    which `NowcastVerifier`, `SpectrumVerifier` and `ValueVerifier` take as they are (`num_members=1`).
+
+`block_match_reference` and `advect_reference` are the specifications in float64 numpy.  On a HIP device the two are
+`dgmr_block_match` and `dgmr_advect` (csrc/advect.hip) on the current stream, without synchronisation; CPU tensors go through the
+references.  Everything else is torch on a lattice of a few thousand nodes, the same code for CPU and HIP tensors.
+"""
+from __future__ import annotations
+
+import ctypes
+from collections import namedtuple
+from typing import Optional
+
+import numpy as np
+import torch
+
+BLOCKS = (16, 32)
+MAX_RADIUS = 16
+MAX_STEPS = 64
+CONTEXT_FRAMES = 4  # at most this many of the latest frames give the motion
+
+BlockMatch = namedtuple("BlockMatch", ["disp", "cost", "wet"])
+
+
+def _check_match(h: int, w: int, block: int, stride: int, radius: int, min_wet: int):
+    if block not in BLOCKS:
+        raise ValueError(f"block={block}, {BLOCKS} are supported")
+    if not 1 <= stride <= block:
+        raise ValueError(f"stride={stride} must be 1 ... block={block}")
+    if not 1 <= radius <= MAX_RADIUS:
+        raise ValueError(f"radius={radius} must be 1 ... {MAX_RADIUS}")
+    if min_wet < 0:
+        raise ValueError(f"min_wet={min_wet} must not be negative")
+    if h < block or w < block:
+        raise ValueError(f"H={h} and W={w} must be at least block={block}")
+    return (h - block) // stride + 1, (w - block) // stride + 1
+
+
+def _tie_order(radius: int):
+    """The candidates (dy, dx) in the order ties are resolved: smallest dy^2 + dx^2, then smallest dy, then smallest dx."""
+    d = [(dy, dx) for dy in range(-radius, radius + 1) for dx in range(-radius, radius + 1)]
+    return sorted(d, key=lambda v: (v[0] * v[0] + v[1] * v[1], v[0], v[1]))
+
+
+def block_costs_reference(prev, nxt, block: int, stride: int, radius: int) -> np.ndarray:
+    """float64 [N, By, Bx, 2R + 1, 2R + 1]: the cost of every displacement (index dy + R, dx + R), +inf where it is no candidate."""
+    p = np.asarray(prev, dtype=np.float32)
+    q = np.asarray(nxt, dtype=np.float32)
+    n, h, w = p.shape
+    by, bx = (h - block) // stride + 1, (w - block) // stride + 1
+    with np.errstate(invalid="ignore"):
+        p = np.where(p >= 0, p, np.float32(0)).astype(np.float64)
+        q = np.where(q >= 0, q, np.float32(0)).astype(np.float64)
+    pad = np.zeros((n, h + 2 * radius, w + 2 * radius))
+    pad[:, radius:radius + h, radius:radius + w] = p
+    y0 = np.arange(by) * stride
+    x0 = np.arange(bx) * stride
+    d = 2 * radius + 1
+    costs = np.full((n, by, bx, d, d), np.inf)
+    view = np.lib.stride_tricks.sliding_window_view
+    for dy in range(-radius, radius + 1):
+        ok_y = (y0 - dy >= 0) & (y0 - dy + block <= h)
+        for dx in range(-radius, radius + 1):
+            ok_x = (x0 - dx >= 0) & (x0 - dx + block <= w)
+            if not ok_y.any() or not ok_x.any():
+                continue
+            diff = q - pad[:, radius - dy:radius - dy + h, radius - dx:radius - dx + w]  # prev[y - dy][x - dx]
+            sums = view(diff * diff, (block, block), axis=(1, 2))[:, ::stride, ::stride].sum(axis=(-1, -2))
+            costs[:, :, :, dy + radius, dx + radius] = np.where(ok_y[None, :, None] & ok_x[None, None, :], sums, np.inf)
+    return costs
+
+
+def block_match_reference(prev, nxt, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
+                          min_wet: int = 64, costs: Optional[np.ndarray] = None) -> BlockMatch:
+    """The specification of `dgmr_block_match`, in float64 numpy.
+
+    prev, nxt: fp32 [N, H, W]; an element with `!(x >= 0)` is missing and read as 0.  Blocks of block x block pixels with top-left
+    corners at (by stride, bx stride), By = (H - block) // stride + 1, Bx likewise.  Per plane and block:
+
+      wet[N, By, Bx]      int32    elements of the `nxt` block (missing as 0) that are >= wet_threshold, compared in fp32
+      disp[N, By, Bx, 2]  int32    (dy, dx), |dy|, |dx| <= radius, of least cost among the candidates - those whose displaced block
+                                   prev[y0 - dy ...][x0 - dx ...] lies wholly inside the frame; cost = sum over the block of
+                                   (nxt[y0 + i][x0 + j] - prev[y0 - dy + i][x0 - dx + j])^2.  Ties: the smallest dy^2 + dx^2, then
+                                   the smallest dy, then the smallest dx
+      cost[N, By, Bx, 5]  float64  the minimum and the costs at (dy - 1, dx), (dy + 1, dx), (dy, dx - 1), (dy, dx + 1); +inf where
+                                   that neighbour is no candidate
+    A block with wet < min_wet is dry: disp = (0, 0), all five costs +inf.  `costs`: a `block_costs_reference` result to reuse."""
+    q = np.asarray(nxt, dtype=np.float32)
+    if q.ndim != 3 or np.shape(prev) != q.shape:
+        raise ValueError(f"prev and nxt must be [N, H, W] of one shape, got {np.shape(prev)} and {q.shape}")
+    n, h, w = q.shape
+    by, bx = _check_match(h, w, block, stride, radius, min_wet)
+    with np.errstate(invalid="ignore"):
+        q0 = np.where(q >= 0, q, np.float32(0))
+        is_wet = q0 >= np.float32(wet_threshold)
+    wet = np.lib.stride_tricks.sliding_window_view(is_wet, (block, block), axis=(1, 2))[:, ::stride, ::stride].sum(axis=(-1, -2))
+    wet = wet.astype(np.int32)
+    if costs is None:
+        costs = block_costs_reference(prev, nxt, block, stride, radius)
+    order = _tie_order(radius)
+    oy = np.array([v[0] for v in order])
+    ox = np.array([v[1] for v in order])
+    ranked = costs[:, :, :, oy + radius, ox + radius]  # [N, By, Bx, candidates in tie order]
+    first = np.argmin(ranked, axis=-1)                 # the first of equal minima: the tie rule
+    dy, dx = oy[first], ox[first]
+    big = np.full((n, by, bx, 2 * radius + 3, 2 * radius + 3), np.inf)
+    big[:, :, :, 1:-1, 1:-1] = costs
+    ii = np.indices((n, by, bx))
+    cost = np.stack([big[ii[0], ii[1], ii[2], dy + radius + 1 + a, dx + radius + 1 + b]
+                     for a, b in ((0, 0), (-1, 0), (1, 0), (0, -1), (0, 1))], axis=-1)
+    dry = wet < min_wet
+    disp = np.stack([dy, dx], axis=-1).astype(np.int32)
+    disp[dry] = 0
+    cost[dry] = np.inf
+    return BlockMatch(disp, cost, wet)
+
+
+def _lattice_axis(q, origin: float, spacing: float, g: int):
+    gc = np.clip((q - origin) / spacing, 0.0, g - 1.0)
+    i0 = np.minimum(np.floor(gc).astype(np.int64), max(g - 2, 0))
+    return i0, np.minimum(i0 + 1, g - 1), gc - i0
+
+
+def _field_at(field, py, px, origin, spacing):
+    """Bilinear interpolation of field [Gy, Gx, 2] at pixel positions (py, px), clamped to the lattice's extent."""
+    y0, y1, fy = _lattice_axis(py, origin, spacing, field.shape[0])
+    x0, x1, fx = _lattice_axis(px, origin, spacing, field.shape[1])
+    fy, fx = fy[..., None], fx[..., None]
+    top = field[y0, x0] + fx * (field[y0, x1] - field[y0, x0])
+    bot = field[y1, x0] + fx * (field[y1, x1] - field[y1, x0])
+    return top + fy * (bot - top)
+
+
+def _sample(x, sy, sx):
+    """Bilinear interpolation of x [H, W] at (sy, sx); a tap outside the frame is 0."""
+    h, w = x.shape
+    sy = np.clip(sy, -2.0, h + 1.0)
+    sx = np.clip(sx, -2.0, w + 1.0)
+    iy, ix = np.floor(sy).astype(np.int64), np.floor(sx).astype(np.int64)
+    fy, fx = sy - iy, sx - ix
+    pad = np.zeros((h + 6, w + 6))
+    pad[3:3 + h, 3:3 + w] = x
+
+    def tap(a, b):
+        return pad[a + 3, b + 3]
+
+    top = tap(iy, ix) + fx * (tap(iy, ix + 1) - tap(iy, ix))
+    bot = tap(iy + 1, ix) + fx * (tap(iy + 1, ix + 1) - tap(iy + 1, ix))
+    return top + fy * (bot - top)
+
+
+def advect_reference(x, field, steps: int, origin: float = 0.0, spacing: float = 1.0) -> np.ndarray:
+    """The specification of `dgmr_advect`, in float64 numpy -> float64 [N, steps, H, W].
+
+    x: fp32 [N, H, W], missing elements (`!(x >= 0)`) read as 0.  field: [N or 1, Gy, Gx, 2] = (vy, vx) in pixels per step; node
+    (gy, gx) sits at pixel (origin + gy spacing, origin + gx spacing); one plane is shared by all planes of x.  v(p): bilinear
+    interpolation of the lattice with positions clamped to its extent (Gy = Gx = 1: a uniform field); s(p): bilinear interpolation
+    of x, a tap outside the frame is 0, so the forecast ramps to zero over one pixel where nothing can be advected in.
+    D_0 = 0;  D_t(p) = D_(t-1)(p) + v(p - D_(t-1)(p));  out[n, t - 1][p] = s(p - D_t(p)): every lead time interpolates the source once."""
+    x = np.asarray(x, dtype=np.float32)
+    field = np.asarray(field, dtype=np.float32).astype(np.float64)
+    if x.ndim != 3 or field.ndim != 4 or field.shape[-1] != 2 or field.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"x must be [N, H, W] and field [N or 1, Gy, Gx, 2], got {x.shape} and {field.shape}")
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"steps={steps}, 1 ... {MAX_STEPS} are supported")
+    if not spacing > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    origin, spacing = float(np.float32(origin)), float(np.float32(spacing))
+    n, h, w = x.shape
+    with np.errstate(invalid="ignore"):
+        x = np.where(x >= 0, x, np.float32(0)).astype(np.float64)
+    py, px = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    out = np.empty((n, steps, h, w))
+    for i in range(n):
+        f = field[i if field.shape[0] > 1 else 0]
+        dy, dx = np.zeros((h, w)), np.zeros((h, w))
+        for t in range(steps):
+            v = _field_at(f, py - dy, px - dx, origin, spacing)
+            dy, dx = dy + v[..., 0], dx + v[..., 1]
+            out[i, t] = _sample(x[i], py - dy, px - dx)
+    return out
+
+
+# ---- the device path -------------------------------------------------------------------------------------------------------------
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _planes(t: torch.Tensor, what: str):
+    """[N, H, W] fp32 with contiguous planes -> (tensor, plane stride); any other layout is copied."""
+    if t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"{what} must be a float32 [N, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
+    h, w = t.shape[1:]
+    if (w > 1 and t.stride(2) != 1) or (h > 1 and t.stride(1) != w) or (t.shape[0] > 1 and t.stride(0) < 0):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else h * w)
+
+
+def block_match(prev: torch.Tensor, nxt: torch.Tensor, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
+                min_wet: Optional[int] = None) -> BlockMatch:
+    """`block_match_reference` for torch tensors, results on the inputs' device: disp int32 [N, By, Bx, 2], cost fp32 [N, By, Bx, 5],
+    wet int32 [N, By, Bx].  prev, nxt: fp32 [N, H, W] whose planes are contiguous and equally far apart in both (views of one
+    [T, N, H, W] tensor are; anything else is copied).  min_wet: default block^2 // 16.  On a HIP device one `dgmr_block_match` on
+    the current stream, nothing synchronised; on the CPU the float64 reference, its costs rounded to fp32."""
+    min_wet = block * block // 16 if min_wet is None else int(min_wet)
+    if prev.shape != nxt.shape or prev.device != nxt.device:
+        raise ValueError(f"prev {tuple(prev.shape)} on {prev.device} and nxt {tuple(nxt.shape)} on {nxt.device} must match")
+    prev, ps = _planes(prev, "prev")
+    nxt, ns = _planes(nxt, "nxt")
+    n, h, w = (int(v) for v in prev.shape)
+    by, bx = _check_match(h, w, block, stride, radius, min_wet)
+    if not prev.is_cuda:
+        ref = block_match_reference(prev.numpy(), nxt.numpy(), block, stride, radius, wet_threshold, min_wet)
+        return BlockMatch(torch.from_numpy(ref.disp), torch.from_numpy(ref.cost.astype(np.float32)), torch.from_numpy(ref.wet))
+    from ._lib import call
+
+    if ps != ns:
+        prev, nxt = prev.contiguous(), nxt.contiguous()
+        ps = h * w
+    device = prev.device
+    with torch.cuda.device(device):
+        disp = torch.empty((n, by, bx, 2), dtype=torch.int32, device=device)
+        cost = torch.empty((n, by, bx, 5), dtype=torch.float32, device=device)
+        wet = torch.empty((n, by, bx), dtype=torch.int32, device=device)
+        call("dgmr_block_match", prev.data_ptr(), nxt.data_ptr(), ps, n, h, w, block, stride, radius, float(wet_threshold), min_wet,
+             disp.data_ptr(), cost.data_ptr(), wet.data_ptr(), _stream(device))
+    return BlockMatch(disp, cost, wet)
+
+
+def advect(x: torch.Tensor, field: torch.Tensor, steps: int, origin: float = 0.0, spacing: float = 1.0,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`advect_reference` for torch tensors -> fp32 [N, steps, H, W] on the inputs' device.
+
+    x: fp32 [N, H, W] (contiguous planes, any plane stride); field: fp32 [N or 1, Gy, Gx, 2].  out: an fp32 [N, steps, H, W] tensor or
+    view whose planes are contiguous, with any strides over N and steps - a permuted view of a [B, T, C, H, W] buffer is written in
+    place.  On a HIP device one `dgmr_advect` on the current stream, nothing synchronised; on the CPU the float64 reference, rounded."""
+    x, xs = _planes(x, "x")
+    n, h, w = (int(v) for v in x.shape)
+    if field.dim() != 4 or field.shape[-1] != 2 or field.shape[0] not in (1, n) or field.dtype != torch.float32 or field.device != x.device:
+        raise ValueError(f"field must be a float32 [{n} or 1, Gy, Gx, 2] tensor on {x.device}, got {field.dtype} {tuple(field.shape)}")
+    steps = int(steps)
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"steps={steps}, 1 ... {MAX_STEPS} are supported")
+    if not float(spacing) > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    if out is None:
+        out = torch.empty((n, steps, h, w), dtype=torch.float32, device=x.device)
+    elif (tuple(out.shape) != (n, steps, h, w) or out.dtype != torch.float32 or out.device != x.device or (w > 1 and out.stride(3) != 1)
+          or (h > 1 and out.stride(2) != w) or (n > 1 and out.stride(0) < 0) or (steps > 1 and out.stride(1) < h * w)):
+        raise ValueError(f"out must be a float32 [{n}, {steps}, {h}, {w}] tensor on {x.device} with contiguous planes")
+    if not x.is_cuda:
+        ref = advect_reference(x.numpy(), field.numpy(), steps, origin, spacing)
+        out.copy_(torch.from_numpy(ref.astype(np.float32)))
+        return out
+    from ._lib import call
+
+    if not field[0].is_contiguous() or (field.shape[0] > 1 and field.stride(0) < 0):
+        field = field.contiguous()
+    fs = int(field.stride(0)) if field.shape[0] > 1 else 0
+    device = x.device
+    with torch.cuda.device(device):
+        call("dgmr_advect", x.data_ptr(), xs if n > 1 else 0, field.data_ptr(), fs, n, h, w, int(field.shape[1]), int(field.shape[2]),
+             float(origin), float(spacing), steps, out.data_ptr(), int(out.stride(0)) if n > 1 else 0,
+             int(out.stride(1)) if steps > 1 else h * w, _stream(device))
+    return out
+
+
+# ---- motion field ----------------------------------------------------------------------------------------------------------------
+def _box_sum(a: torch.Tensor, radius: int) -> torch.Tensor:
+    """Sums over (2 radius + 1)^2 lattice nodes around every node of a [..., By, Bx] tensor (zeros beyond the edge), by prefix sums."""
+    for dim in (-2, -1):
+        size = a.shape[dim]
+        pad = [0, 0] * a.dim()
+        pad[2 * (-dim - 1)] = radius + 1
+        pad[2 * (-dim - 1) + 1] = radius
+        cs = torch.nn.functional.pad(a, pad).cumsum(dim)
+        a = cs.narrow(dim, 2 * radius + 1, size) - cs.narrow(dim, 0, size)
+    return a
+
+
+def _subpixel(c0, cm, cp):
+    """The minimum of the parabola through the costs at -1, 0, +1, clipped to +-0.5; 0 where the three do not curve upwards."""
+    den = cm - 2.0 * c0 + cp
+    ok = den > 0
+    return torch.where(ok, (0.5 * (cm - cp) / torch.where(ok, den, torch.ones_like(den))).clamp(-0.5, 0.5), torch.zeros_like(den))
+
+
+def motion_field(frames: torch.Tensor, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
+                 min_wet: Optional[int] = None, smooth: int = 2) -> torch.Tensor:
+    """Motion in pixels per frame on the block lattice: fp32 [N, By, Bx, 2] = (vy, vx); node (by, bx) stands for the block's centre,
+    pixel ((block - 1) / 2 + by stride, (block - 1) / 2 + bx stride) - `advect`'s origin and spacing (`lattice_geometry`).
+
+    frames: fp32 [T_in >= 2, N, H, W], the context in time order.  One `block_match` call over all T_in - 1 consecutive pairs and all
+    planes.  A block of a pair is usable when it is not dry and its minimum is interior (all four neighbour costs finite); its
+    vector is the integer displacement plus, per axis, clip(0.5 (c- - c+) / (c- - 2 c0 + c+), +-0.5) where that denominator is
+    positive (else 0).  The pairs are averaged, weighted by usability; then a normalised box smoothing over (2 smooth + 1)^2 nodes,
+    sum w v / sum w with w = 1 at nodes that had a usable pair; nodes with no usable neighbour take the plane's mean usable vector,
+    (0, 0) if there is none.  All of this after `block_match` is torch in float64 on the lattice, on the frames' device."""
+    if frames.dim() != 4 or frames.shape[0] < 2 or frames.dtype != torch.float32:
+        raise ValueError(f"frames must be a float32 [T_in >= 2, N, H, W] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if smooth < 0:
+        raise ValueError(f"smooth={smooth} must not be negative")
+    frames = frames.contiguous()
+    pairs, n, h, w = frames.shape[0] - 1, *(int(v) for v in frames.shape[1:])
+    res = block_match(frames[:-1].reshape(pairs * n, h, w), frames[1:].reshape(pairs * n, h, w), block, stride, radius, wet_threshold,
+                      min_wet)
+    by, bx = res.wet.shape[1:]
+    cost = res.cost.view(pairs, n, by, bx, 5).to(torch.float64)
+    disp = res.disp.view(pairs, n, by, bx, 2).to(torch.float64)
+    usable = torch.isfinite(cost).all(dim=-1)
+    c = torch.where(usable[..., None], cost, torch.zeros_like(cost))
+    v = disp + torch.stack([_subpixel(c[..., 0], c[..., 1], c[..., 2]), _subpixel(c[..., 0], c[..., 3], c[..., 4])], dim=-1)
+    u = usable.to(torch.float64)
+    count = u.sum(dim=0)                                   # [N, By, Bx]
+    have = count > 0
+    mean = (v * u[..., None]).sum(dim=0) / count.clamp_min(1.0)[..., None]
+    wgt = have.to(torch.float64)
+    num = _box_sum((mean * wgt[..., None]).permute(0, 3, 1, 2), smooth).permute(0, 2, 3, 1)
+    den = _box_sum(wgt, smooth)
+    total = wgt.sum(dim=(1, 2))
+    plane_mean = (mean * wgt[..., None]).sum(dim=(1, 2)) / total.clamp_min(1.0)[:, None]  # (0, 0) without a usable node
+    near = den > 0.5
+    field = torch.where(near[..., None], num / den.clamp_min(1.0)[..., None], plane_mean[:, None, None, :].expand_as(num))
+    return field.to(torch.float32).contiguous()
+
+
+def lattice_geometry(block: int, stride: int):
+    """(origin, spacing) of `motion_field`'s lattice for `advect`: the block centres."""
+    return (block - 1) / 2.0, float(stride)
+
+
+def persistence_nowcast(last: torch.Tensor, forecast_steps: int) -> torch.Tensor:
+    """Eulerian persistence: last [C, H, W] -> [1, T, C, H, W]; last [B, C, H, W] -> [1, B, T, C, H, W] - the last frame at every lead
+    time, as an expanded VIEW of one copy in which missing elements (`!(x >= 0)`) are 0."""
+    if last.dim() not in (3, 4):
+        raise ValueError(f"last must be [C, H, W] or [B, C, H, W], got shape {tuple(last.shape)}")
+    x = torch.where(last >= 0, last, torch.zeros_like(last)).float()
+    if last.dim() == 3:
+        return x[None, None].expand(1, int(forecast_steps), *x.shape)
+    return x[None, :, None].expand(1, x.shape[0], int(forecast_steps), *x.shape[1:])
+
+
+class AdvectionNowcaster:
+    """Lagrangian persistence: the motion of the last (at most 4) context frames by `motion_field`, the last frame extrapolated along
+    it by `advect` for `forecast_steps` lead times.  One member: no growth or decay, no perturbation.  `last_field`: the motion field
+    of the latest call, [planes, By, Bx, 2] in pixels per frame, planes in (B, C) order."""
+
+    def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
+                 min_wet: Optional[int] = None, smooth: int = 2):
+        if not 1 <= int(forecast_steps) <= MAX_STEPS:
+            raise ValueError(f"forecast_steps={forecast_steps}, 1 ... {MAX_STEPS} are supported")
+        self.forecast_steps = int(forecast_steps)
+        self.params = dict(block=block, stride=stride, radius=radius, wet_threshold=wet_threshold, min_wet=min_wet, smooth=smooth)
+        self.last_field = None
+
+    def _run(self, context: torch.Tensor, out: torch.Tensor, planes_per_case: int) -> None:
+        """context [T_in, B * C, H, W]; out [B, T, C, H, W]"""
+        self.last_field = motion_field(context[-CONTEXT_FRAMES:], **self.params)
+        origin, spacing = lattice_geometry(self.params["block"], self.params["stride"])
+        b, c = out.shape[0], planes_per_case
+        last = context[-1].view(b, c, *context.shape[2:])
+        field = self.last_field.view(b, c, *self.last_field.shape[1:])
+        for ch in range(c):  # planes of one channel are equally far apart in the output: one launch per channel
+            advect(last[:, ch], field[:, ch], self.forecast_steps, origin, spacing, out=out[:, :, ch])
+
+    def nowcast(self, frames, scale: float = 1.0, offset: float = 0.0) -> torch.Tensor:
+        """frames [T_in >= 2, H, W, C] in a storage dtype (numpy or torch; converted as `verification.observed_from_frames` does,
+        missing elements stay missing for the matching's rule) -> fp32 [1, forecast_steps, C, H, W] on the frames' device."""
+        from .verification import observed_from_frames
+
+        x = observed_from_frames(frames, scale, offset)  # [T_in, C, H, W]
+        if x.shape[0] < 2:
+            raise ValueError(f"frames holds {x.shape[0]} frames, the motion needs 2")
+        out = torch.empty((1, self.forecast_steps) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+        self._run(x, out, int(x.shape[1]))
+        return out
+
+    def nowcast_batch(self, images: torch.Tensor) -> torch.Tensor:
+        """images fp32 [B, T_in >= 2, C, H, W] -> fp32 [1, B, forecast_steps, C, H, W]."""
+        if images.dim() != 5 or images.shape[1] < 2 or images.dtype != torch.float32:
+            raise ValueError(f"images must be a float32 [B, T_in >= 2, C, H, W] tensor, got {images.dtype} {tuple(images.shape)}")
+        b, _, c, h, w = images.shape
+        context = images[:, -CONTEXT_FRAMES:].permute(1, 0, 2, 3, 4).reshape(-1, b * c, h, w).contiguous()
+        out = torch.empty((1, b, self.forecast_steps, c, h, w), dtype=torch.float32, device=images.device)
+        self._run(context, out[0], int(c))
+        return out

@@ -352,3 +352,26 @@ def _rank_histogram(ranks: np.ndarray) -> np.ndarray:
             hist[:, b:b + e + 1] += (ranks[:, b, e] / (e + 1))[:, None]
     with np.errstate(divide="ignore", invalid="ignore"):
         return hist / hist.sum(axis=1, keepdims=True)
+
+
+def skill_score(metrics: dict, baseline_metrics: dict) -> dict:
+    """A forecast's `NowcastVerifier.compute()` result against a baseline's (advection.py: `AdvectionNowcaster`, `persistence_nowcast`)
+    over the same cases, with the same scales and thresholds:
+      crps[pool][scale] -> [T]   1 - crps / crps_baseline: positive where the forecast beats the baseline, 1 for a perfect one; NaN
+                                 where the baseline's CRPS is 0 or either is NaN
+      csi[threshold] -> [T]      csi - csi_baseline"""
+    res = {"crps": {}, "csi": {}}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for pool, per_scale in metrics["crps"].items():
+            base = baseline_metrics["crps"][pool]
+            if set(base) != set(per_scale):
+                raise ValueError(f"skill_score: scales {sorted(per_scale)} against the baseline's {sorted(base)}")
+            res["crps"][pool] = {}
+            for s, v in per_scale.items():
+                b = np.asarray(base[s], dtype=np.float64)
+                res["crps"][pool][s] = np.where(b != 0, 1.0 - np.asarray(v, dtype=np.float64) / np.where(b != 0, b, 1.0), np.nan)
+        if set(metrics["csi"]) != set(baseline_metrics["csi"]):
+            raise ValueError(f"skill_score: thresholds {sorted(metrics['csi'])} against the baseline's {sorted(baseline_metrics['csi'])}")
+        for t, v in metrics["csi"].items():
+            res["csi"][t] = np.asarray(v, dtype=np.float64) - np.asarray(baseline_metrics["csi"][t], dtype=np.float64)
+    return res
