@@ -702,6 +702,42 @@ int dgmr_advect(const float* x, int64_t x_plane_stride, const float* field, int6
                 int Gx, float origin, float spacing, int T, float* out, int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The stochastic advection ensemble (stochastic.py; csrc/spectrum.hip, csrc/advect.hip).  New symbols, same ABI version.
+ *
+ * dgmr_spectral_ar: an AR(1) process per Fourier mode of overlapping L x L windows, L one of 32, 64, 128, blended to full planes.
+ * z0: P fp32 planes [H][W], z0_plane_stride apart, any real values (no missing-value rule).  white: plane n = p M + m of lead time t
+ * at white + n white_member_stride + (t - 1) white_step_stride; out likewise with its two strides.  rho: L fp32 values in [-1, 1].
+ * H and W multiples of L, 1 <= T <= 64.  Windows in four classes (cy, cx), cy, cx in {0, 1}: the origins of a class are
+ * (i L + cy L / 2, j L + cx L / 2), i < H / L - cy, j < W / L - cx.  Per window and member, with U = fft2(z0 patch), A = |U| / L,
+ * X_0 = U and Wh_t = fft2(white patch of lead t):
+ *   X_t(k) = rho[r(k)] X_(t-1)(k) + sqrt(1 - rho[r(k)]^2) A(k) Wh_t(k),   x_t = real(ifft2(X_t)),   t = 1 ... T,
+ * r(k) the radial bin of dgmr_radial_psd (r (r - 1) < kx^2 + ky^2 <= r (r + 1) over the signed frequencies in [-L/2, L/2); r < L).
+ * Blend weights per axis, multiplied: an offset window (class index 1 on the axis) has h(i) = sin^2(pi (i + 1/2) / L) at local
+ * index i, computed in double and rounded to fp32; an aligned window has 1 - h(i') (fp32), i' the pixel's index in the offset
+ * window that covers it on that axis, and 1 in the outer L / 2 of the frame where there is none.  out[n][t - 1] = the weighted sum
+ * of the at most four windows over a pixel.  fp32 radix-2 transforms in LDS (the PSD's forward DIF with the Nyquist column carried,
+ * a DIT from the bit-reversed positions back), the window's spectrum and noise amplitudes in registers through the T steps,
+ * sqrt(1 - rho^2) formed in double.  One workgroup per (plane, member, window); four launches, one per class in the order (0,0),
+ * (0,1), (1,0), (1,1): the first stores, the others read, add (one fma) and write, and windows of a class are disjoint - no atomics,
+ * two calls give the same bits.  16-byte accesses when pointers and strides allow them (z0 and white together, out on its own),
+ * 4-byte accesses otherwise.  Argument errors (null pointers, L outside the set, H or W not a multiple of L, T outside 1 ... 64, a
+ * white or out stride below H * W) return < 0 and set dgmr_last_error() before anything is enqueued.  Runs on `stream`, does not
+ * synchronise.
+ *
+ * dgmr_advect_series: dgmr_advect with a source of its own per lead time - lead t of plane n samples
+ * x + n x_plane_stride + (t - 1) x_step_stride - and with plane n reading field plane n / field_group (the members of an ensemble
+ * share their case's motion).  Every source value below 0 (or NaN) reads as 0.  Everything else - the D_t recursion, the arithmetic,
+ * the store widths, the bound with A and max|x| taken over all steps' sources, the refusals - is dgmr_advect's;
+ * x_step_stride = 0 with field_group = 1 gives dgmr_advect's bits.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const float* white, int64_t white_member_stride, int64_t white_step_stride,
+                     const float* rho, int P, int M, int T, int H, int W, int L, float* out, int64_t out_member_stride,
+                     int64_t out_step_stride, void* stream);
+int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_t x_step_stride, const float* field, int64_t field_plane_stride,
+                       int field_group, int64_t N, int H, int W, int Gy, int Gx, float origin, float spacing, int T, float* out,
+                       int64_t out_plane_stride, int64_t out_step_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

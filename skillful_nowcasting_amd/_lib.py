@@ -159,6 +159,8 @@ SIGNATURES = {
     "dgmr_exceedance_table": [P, L, P, i, L, i, i, P, i, P, P],
     "dgmr_block_match": [P, P, L, L, i, i, i, i, i, f, i, P, P, P, P],
     "dgmr_advect": [P, L, P, L, L, i, i, i, i, f, f, i, P, L, L, P],
+    "dgmr_spectral_ar": [P, L, P, L, L, P, i, i, i, i, i, i, P, L, L, P],
+    "dgmr_advect_series": [P, L, L, P, L, i, L, i, i, i, i, f, f, i, P, L, L, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],

@@ -6,6 +6,8 @@ paper plots DGMR against; INTEGRATION.md "A baseline to beat").
   * `motion_field`: block matching over consecutive context frames, a parabola through the neighbour costs for the sub-pixel part,
     the pairs averaged, the lattice smoothed and filled;
   * `advect`: the last frame extrapolated along the field for all lead times, each lead time interpolating the source once;
+  * `advect_series`: the same with a source of its own per lead time and one field per group of planes (`dgmr_advect_series`) -
+    what `stochastic.EnsembleAdvectionNowcaster` moves its members with;
   * `AdvectionNowcaster`, `persistence_nowcast`: forecasts in the layout of `DGMR.nowcast_full_frame` / `DGMR.sample` with one member,
     which `NowcastVerifier`, `SpectrumVerifier` and `ValueVerifier` take as they are (`num_members=1`).
 
@@ -270,6 +272,82 @@ def advect(x: torch.Tensor, field: torch.Tensor, steps: int, origin: float = 0.0
         call("dgmr_advect", x.data_ptr(), xs if n > 1 else 0, field.data_ptr(), fs, n, h, w, int(field.shape[1]), int(field.shape[2]),
              float(origin), float(spacing), steps, out.data_ptr(), int(out.stride(0)) if n > 1 else 0,
              int(out.stride(1)) if steps > 1 else h * w, _stream(device))
+    return out
+
+
+def advect_series_reference(x, field, origin: float = 0.0, spacing: float = 1.0, field_group: int = 1) -> np.ndarray:
+    """The specification of `dgmr_advect_series`, in float64 numpy -> float64 [N, T, H, W]: `advect_reference` with a source of its
+    own per lead time.
+
+    x: fp32 [N, T, H, W]; every value below 0 (and NaN) reads as 0.  field: [N / field_group or 1, Gy, Gx, 2]: plane n moves along
+    field plane n // field_group.  D_t as in `advect_reference`;  out[n, t - 1][p] = s_t(p - D_t(p)), s_t interpolating x[n, t - 1]."""
+    x = np.asarray(x, dtype=np.float32)
+    field = np.asarray(field, dtype=np.float32).astype(np.float64)
+    field_group = int(field_group)
+    if x.ndim != 4 or field.ndim != 4 or field.shape[-1] != 2 or field_group < 1 or x.shape[0] % field_group or \
+            field.shape[0] not in (1, x.shape[0] // field_group):
+        raise ValueError(f"x must be [N, T, H, W] and field [N / {field_group} or 1, Gy, Gx, 2], got {x.shape} and {field.shape}")
+    n, steps, h, w = x.shape
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if not spacing > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    origin, spacing = float(np.float32(origin)), float(np.float32(spacing))
+    with np.errstate(invalid="ignore"):
+        x = np.where(x >= 0, x, np.float32(0)).astype(np.float64)
+    py, px = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    out = np.empty((n, steps, h, w))
+    for i in range(n):
+        f = field[i // field_group if field.shape[0] > 1 else 0]
+        dy, dx = np.zeros((h, w)), np.zeros((h, w))
+        for t in range(steps):
+            v = _field_at(f, py - dy, px - dx, origin, spacing)
+            dy, dx = dy + v[..., 0], dx + v[..., 1]
+            out[i, t] = _sample(x[i, t], py - dy, px - dx)
+    return out
+
+
+def advect_series(x: torch.Tensor, field: torch.Tensor, origin: float = 0.0, spacing: float = 1.0, field_group: int = 1,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`advect_series_reference` for torch tensors -> fp32 [N, T, H, W] on the inputs' device.
+
+    x: fp32 [N, T, H, W] whose planes are contiguous, with any non-negative strides over N and T (stride 0 over T: one source for all
+    lead times, which is `advect`); any other layout is copied.  field: fp32 [N / field_group or 1, Gy, Gx, 2].  out: as in `advect`.
+    On a HIP device one `dgmr_advect_series` on the current stream, nothing synchronised; on the CPU the float64 reference, rounded."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"x must be a float32 [N, T, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, steps, h, w = (int(v) for v in x.shape)
+    field_group = int(field_group)
+    if field_group < 1 or n % field_group:
+        raise ValueError(f"field_group={field_group} must divide N={n}")
+    planes = n // field_group
+    if field.dim() != 4 or field.shape[-1] != 2 or field.shape[0] not in (1, planes) or field.dtype != torch.float32 or field.device != x.device:
+        raise ValueError(f"field must be a float32 [{planes} or 1, Gy, Gx, 2] tensor on {x.device}, got {field.dtype} {tuple(field.shape)}")
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if not float(spacing) > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    if out is None:
+        out = torch.empty((n, steps, h, w), dtype=torch.float32, device=x.device)
+    elif (tuple(out.shape) != (n, steps, h, w) or out.dtype != torch.float32 or out.device != x.device or (w > 1 and out.stride(3) != 1)
+          or (h > 1 and out.stride(2) != w) or (n > 1 and out.stride(0) < 0) or (steps > 1 and out.stride(1) < h * w)):
+        raise ValueError(f"out must be a float32 [{n}, {steps}, {h}, {w}] tensor on {x.device} with contiguous planes")
+    if not x.is_cuda:
+        ref = advect_series_reference(x.numpy(), field.numpy(), origin, spacing, field_group)
+        out.copy_(torch.from_numpy(ref.astype(np.float32)))
+        return out
+    from ._lib import call
+
+    if (w > 1 and x.stride(3) != 1) or (h > 1 and x.stride(2) != w) or (n > 1 and x.stride(0) < 0) or (steps > 1 and x.stride(1) < 0):
+        x = x.contiguous()
+    if not field[0].is_contiguous() or (field.shape[0] > 1 and field.stride(0) < 0):
+        field = field.contiguous()
+    fs = int(field.stride(0)) if field.shape[0] > 1 else 0
+    device = x.device
+    with torch.cuda.device(device):
+        call("dgmr_advect_series", x.data_ptr(), int(x.stride(0)) if n > 1 else 0, int(x.stride(1)) if steps > 1 else 0, field.data_ptr(),
+             fs, field_group, n, h, w, int(field.shape[1]), int(field.shape[2]), float(origin), float(spacing), steps, out.data_ptr(),
+             int(out.stride(0)) if n > 1 else 0, int(out.stride(1)) if steps > 1 else h * w, _stream(device))
     return out
 
 

@@ -1,5 +1,6 @@
 // The advection baseline on the device (advection.py): block-matching motion between two frames (dgmr_block_match) and the
-// semi-Lagrangian extrapolation of a frame along a motion field for all lead times (dgmr_advect).
+// semi-Lagrangian extrapolation of a frame along a motion field for all lead times (dgmr_advect; dgmr_advect_series: the same with a
+// source of its own per lead time and one field plane per group of planes - stochastic.py's ensemble members).
 //
 // Block matching.  One workgroup per (plane, block).  The `next` block (B x B) is staged in LDS first and its wet elements are
 // counted on the way; a dry block - most of a radar frame - writes its five +inf and leaves before the search window of `prev`
@@ -161,6 +162,8 @@ struct AdvGeom {
     int64_t x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items;
     int H, W, Gy, Gx, T;
     float origin, spacing;
+    int64_t x_step_stride;  // dgmr_advect_series: the source of lead time t is x + (t - 1) x_step_stride ...
+    int field_group;        // ... and plane n reads field plane n / field_group
 };
 
 // lattice coordinate of pixel coordinate q on an axis of G nodes -> the lower node i0, the upper node i1 and the weight of i1
@@ -190,7 +193,8 @@ __device__ __forceinline__ float source_sample(const float* __restrict__ x, int 
     return lerp_fma(top, bot, fy);
 }
 
-template <int V>
+// SERIES = false is dgmr_advect as it always was; SERIES = true adds the per-step source and the shared field plane, nothing else
+template <int V, bool SERIES>
 __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
     const int64_t item = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (item >= g.items) return;
@@ -200,7 +204,7 @@ __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
     const int64_t n = row / g.H;
     const int y = (int)(row - n * g.H);
     const float* __restrict__ x = g.x + n * g.x_plane_stride;
-    const float* __restrict__ fld = g.field + n * g.field_plane_stride;
+    const float* __restrict__ fld = g.field + (SERIES ? n / g.field_group : n) * g.field_plane_stride;
     float* __restrict__ o = g.out + n * g.out_plane_stride + (int64_t)y * g.W + xq;
     const float py = (float)y;
     float Dy[V], Dx[V];
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
             const float vx = lerp_fma(lerp_fma(a[1], b[1], fx), lerp_fma(c[1], d[1], fx), fy);
             Dy[k] += vy;
             Dx[k] += vx;
-            r[k] = source_sample(x, g.H, g.W, py - Dy[k], px - Dx[k]);
+            r[k] = source_sample(SERIES ? x + (int64_t)t * g.x_step_stride : x, g.H, g.W, py - Dy[k], px - Dx[k]);
         }
         float* dst = o + (int64_t)t * g.out_step_stride;
         if constexpr (V == 4) {
@@ -287,12 +291,48 @@ extern "C" int dgmr_advect(const float* x, int64_t x_plane_stride, const float* 
     const int V = wide ? 4 : 1;
     const int64_t items = N * H * (W / V);
     DGMR_CHECK_ARG(items <= (1ll << 38), "%s: %lld pixels are out of range", fn, (long long)(N * H * W));
-    const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing};
+    const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing,
+                    0, 1};
     const dim3 grid((unsigned)((items + 255) / 256)), threads(256);
     if (wide)
-        hipLaunchKernelGGL(advect_kernel<4>, grid, threads, 0, ST, g);
+        hipLaunchKernelGGL((advect_kernel<4, false>), grid, threads, 0, ST, g);
     else
-        hipLaunchKernelGGL(advect_kernel<1>, grid, threads, 0, ST, g);
+        hipLaunchKernelGGL((advect_kernel<1, false>), grid, threads, 0, ST, g);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_t x_step_stride, const float* field, int64_t field_plane_stride,
+                                  int field_group, int64_t N, int H, int W, int Gy, int Gx, float origin, float spacing, int T, float* out,
+                                  int64_t out_plane_stride, int64_t out_step_stride, void* stream) {
+    const char* fn = "dgmr_advect_series";
+    DGMR_CHECK_ARG(x && field && out, "%s: null pointer", fn);
+    DGMR_CHECK_ARG(T >= 1 && T <= 64, "%s: T=%d lead times, 1 ... 64 are supported", fn, T);
+    DGMR_CHECK_ARG(spacing > 0.f && spacing <= 3.0e38f && origin == origin && origin >= -3.0e38f && origin <= 3.0e38f,
+                   "%s: spacing=%g must be positive and finite, origin=%g finite", fn, (double)spacing, (double)origin);
+    DGMR_CHECK_ARG(Gy >= 1 && Gx >= 1 && (int64_t)Gy * Gx <= (1 << 28), "%s: a lattice of %d x %d nodes is out of range", fn, Gy, Gx);
+    DGMR_CHECK_ARG(N >= 1 && N <= (1 << 24), "%s: N=%lld planes out of range", fn, (long long)N);
+    DGMR_CHECK_ARG(field_group >= 1, "%s: field_group=%d must be at least 1", fn, field_group);
+    DGMR_CHECK_ARG(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(x_plane_stride >= 0 && x_plane_stride <= INT64_MAX / 4 / N && field_plane_stride >= 0 &&
+                       field_plane_stride <= INT64_MAX / 4 / N && x_step_stride >= 0 && x_step_stride <= INT64_MAX / 4 / 64,
+                   "%s: x_plane_stride=%lld, x_step_stride=%lld or field_plane_stride=%lld out of range", fn, (long long)x_plane_stride,
+                   (long long)x_step_stride, (long long)field_plane_stride);
+    DGMR_CHECK_ARG(out_plane_stride >= 0 && out_plane_stride <= INT64_MAX / 4 / N && (T == 1 || out_step_stride >= (int64_t)H * W) &&
+                       out_step_stride >= 0 && out_step_stride <= INT64_MAX / 4 / 64,
+                   "%s: out_plane_stride=%lld out of range or out_step_stride=%lld below H * W", fn, (long long)out_plane_stride,
+                   (long long)out_step_stride);
+    const bool wide = W % 4 == 0 && ((uintptr_t)out & 15) == 0 && out_plane_stride % 4 == 0 && out_step_stride % 4 == 0;
+    const int V = wide ? 4 : 1;
+    const int64_t items = N * H * (W / V);
+    DGMR_CHECK_ARG(items <= (1ll << 38), "%s: %lld pixels are out of range", fn, (long long)(N * H * W));
+    const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing,
+                    x_step_stride, field_group};
+    const dim3 grid((unsigned)((items + 255) / 256)), threads(256);
+    if (wide)
+        hipLaunchKernelGGL((advect_kernel<4, true>), grid, threads, 0, ST, g);
+    else
+        hipLaunchKernelGGL((advect_kernel<1, true>), grid, threads, 0, ST, g);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

@@ -1,6 +1,7 @@
 // The two remaining verification plots on the device (spectra.py, value.py): the radially averaged power spectral density of L x L
 // windows (dgmr_radial_psd) and the exceedance table that reliability, Brier score, ROC points and economic value are derived from
-// (dgmr_exceedance_table).
+// (dgmr_exceedance_table).  And, built on the PSD's transforms, the AR(1) noise windows of the stochastic advection ensemble
+// (stochastic.py: dgmr_spectral_ar; its section below says how).
 //
 // PSD.  fp32 radix-2 decimation-in-frequency transforms in LDS (two stages per pass and barrier), twiddles from a table of exp(-2 pi i k / 512) computed in double and
 // rounded to fp32 (psd_twiddle_kernel writes it to the head of the workspace; every kernel copies it to LDS).  The input is real, so
@@ -352,6 +353,276 @@ int psd_run_two_pass(const PsdGeom& g, int64_t nwin, int64_t per_round, const fl
     return 0;
 }
 
+// ---- spectral AR(1) noise windows (stochastic.py) --------------------------------------------------------------------------------------
+// One workgroup per (plane, member, window of one class).  The window's half spectrum X [L][L / 2 + 1] and the noise amplitude
+// g(r) |U| / L of every mode stay in registers through the T steps (element tid + j NT of the LDS layout belongs to thread tid:
+// 17 elements x 4 registers at L = 128 and 512 threads); LDS holds one [L][L / 2 + 1] complex buffer (66 KB at L = 128) that every
+// step fills with the white patch, transforms forward, overwrites with the updated state, transforms back and blends out - two
+// workgroups share a CU.  The layout is the PSD kernel's, with the Nyquist column kx = L / 2 in the padding element of each row, so
+// the column passes run over L / 2 + 1 columns.  The inverse of the DIF transform is a DIT that starts from the bit-reversed
+// positions the DIF leaves: stage by stage the inverse butterfly (p, q) -> (p + q conj w, p - q conj w), which doubles the values -
+// the factor L^2 of both axes is taken out by one exact multiplication in the store.  Twiddles: the table of psd_twiddle_kernel,
+// computed by every workgroup for itself (256 double sincospi against T forward and inverse transforms).
+// Blend: four launches, classes (0,0), (0,1), (1,0), (1,1) in stream order; the first stores value * weight, the others read, fma and
+// write.  Windows of one class are disjoint, so no two workgroups of a launch touch one element: no atomics, the same bits every call.
+struct ArGeom {
+    const float* z0;
+    const float* white;
+    const float* rho;
+    float* out;
+    int64_t z0_plane_stride, white_member_stride, white_step_stride, out_member_stride, out_step_stride;
+    int M, T, H, W, cy, cx, wins_y, wins_x;  // wins: the windows of this class per plane
+    int wide_in, wide_out;                   // 16-byte accesses allowed for z0 and white / for out
+};
+
+constexpr int ar_state(int L) { return (L * (L / 2 + 1) + psd_threads(L) - 1) / psd_threads(L); }
+
+template <int L>
+constexpr int ar_lds() { return L * (L / 2 + 1) * 8 + PSD_TW * 8 + 4 * L * 4; }
+
+// fft_dif undone: frequency k is read from element brev(k), sample n of 2^stages times the inverse lands at element n.
+template <int N, int NF, int SE, int SF, int NT>
+__device__ __forceinline__ void fft_dit_inverse(float2* __restrict__ s, const float2* __restrict__ tw, int tid) {
+    constexpr int TWS = 512 / N;
+    constexpr bool ODD = (ilog2(N) & 1) != 0;
+    // fft_dif's passes backwards: its single last stage (distance 1, when log2 N is odd) first, then its two-stage passes from
+    // the shortest distances to the longest, each pass undoing the stage of distance q = h / 2 and then the one of distance h
+    if (ODD) {
+        for (int t = tid; t < NF * (N / 2); t += NT) {
+            const int f = t % NF, j = t / NF;
+            float2* p = s + f * SF + 2 * j * SE;
+            const float2 u = p[0], v = p[SE];  // twiddle 1
+            p[0] = make_float2(u.x + v.x, u.y + v.y);
+            p[SE] = make_float2(u.x - v.x, u.y - v.y);
+        }
+        __syncthreads();
+    }
+#pragma unroll 1
+    for (int h = ODD ? 4 : 2; h <= N / 2; h <<= 2) {
+        const int q = h >> 1, tstep = (N / (2 * h)) * TWS;
+        for (int t = tid; t < NF * (N / 4); t += NT) {
+            const int f = t % NF, j = t / NF;
+            const int i = j & (q - 1);
+            const int a = ((j - i) << 2) + i;  // < N - 3 q
+            float2* p = s + f * SF + a * SE;
+            const float2 z0 = p[0], z1 = p[q * SE], z2 = p[2 * q * SE], z3 = p[3 * q * SE];
+            const float2 wa = tw[i * tstep], wb = tw[i * tstep + 128], wc = tw[2 * i * tstep];
+            const float ax = z1.x * wc.x + z1.y * wc.y, ay = z1.y * wc.x - z1.x * wc.y;  // z1 conj(wc)
+            const float bx = z3.x * wc.x + z3.y * wc.y, by = z3.y * wc.x - z3.x * wc.y;  // z3 conj(wc)
+            const float2 y0 = make_float2(z0.x + ax, z0.y + ay), y1 = make_float2(z0.x - ax, z0.y - ay);
+            const float2 y2 = make_float2(z2.x + bx, z2.y + by), y3 = make_float2(z2.x - bx, z2.y - by);
+            const float cx = y2.x * wa.x + y2.y * wa.y, cy = y2.y * wa.x - y2.x * wa.y;  // y2 conj(wa)
+            const float dx = y3.x * wb.x + y3.y * wb.y, dy = y3.y * wb.x - y3.x * wb.y;  // y3 conj(wb)
+            p[0] = make_float2(y0.x + cx, y0.y + cy);
+            p[q * SE] = make_float2(y1.x + dx, y1.y + dy);
+            p[2 * q * SE] = make_float2(y0.x - cx, y0.y - cy);
+            p[3 * q * SE] = make_float2(y1.x - dx, y1.y - dy);
+        }
+        __syncthreads();
+    }
+}
+
+// real_split that also forms the Nyquist column: X[L / 2] = Re Z[0] - Im Z[0] goes to element L / 2 of the row.
+template <int L, int NF, int SF, int NT>
+__device__ __forceinline__ void real_split_nyquist(float2* __restrict__ s, const float2* __restrict__ tw, int tid) {
+    constexpr int NH = L / 2, BITS = ilog2(NH), TWS = 512 / L;
+    for (int t = tid; t < NF * (NH / 2 + 1); t += NT) {
+        const int f = t % NF, k = t / NF;
+        float2* row = s + f * SF;
+        if (k == 0) {
+            const float2 z = row[0];
+            row[0] = make_float2(z.x + z.y, 0.f);
+            row[NH] = make_float2(z.x - z.y, 0.f);
+        } else {
+            const int pa = brev<BITS>(k), pb = brev<BITS>(NH - k);
+            const float2 za = row[pa], zb = row[pb];
+            const float ex = 0.5f * (za.x + zb.x), ey = 0.5f * (za.y - zb.y);
+            const float ox = 0.5f * (za.y + zb.y), oy = -0.5f * (za.x - zb.x);
+            const float2 w = tw[k * TWS];
+            const float tx = w.x * ox - w.y * oy, ty = w.x * oy + w.y * ox;
+            row[pa] = make_float2(ex + tx, ey + ty);
+            if (pb != pa) row[pb] = make_float2(ex - tx, ty - ey);
+        }
+    }
+    __syncthreads();
+}
+
+// real_split_nyquist undone, up to a factor 2: X[kx] at element brev(kx) (kx = L / 2 at element L / 2) -> 2 Z[k] at element brev(k),
+// Z the transform of z[m] = x[2m] + i x[2m + 1].  With S = X[k] + conj X[NH - k] and D = (X[k] - conj X[NH - k]) conj W_L^k:
+// 2 Z[k] = S + i D,  2 Z[NH - k] = conj S + i conj D.  Only the real parts of X[0] and X[L / 2] enter: the result is real(ifft2).
+template <int L, int NF, int SF, int NT>
+__device__ __forceinline__ void real_merge(float2* __restrict__ s, const float2* __restrict__ tw, int tid) {
+    constexpr int NH = L / 2, BITS = ilog2(NH), TWS = 512 / L;
+    for (int t = tid; t < NF * (NH / 2 + 1); t += NT) {
+        const int f = t % NF, k = t / NF;
+        float2* row = s + f * SF;
+        if (k == 0) {
+            const float x0 = row[0].x, xn = row[NH].x;
+            row[0] = make_float2(x0 + xn, x0 - xn);
+        } else {
+            const int pa = brev<BITS>(k), pb = brev<BITS>(NH - k);
+            const float2 a = row[pa], b = row[pb];
+            const float sx = a.x + b.x, sy = a.y - b.y;
+            const float dx = a.x - b.x, dy = a.y + b.y;
+            const float2 w = tw[k * TWS];
+            const float tx = dx * w.x + dy * w.y, ty = dy * w.x - dx * w.y;  // D conj(w)
+            row[pa] = make_float2(sx - ty, sy + tx);
+            if (pb != pa) row[pb] = make_float2(sx + ty, tx - sy);
+        }
+    }
+    __syncthreads();
+}
+
+// an L x L patch at `src` (row pitch W) -> s[y * RS + m] = (x[y][2m], x[y][2m + 1]), every value as it is
+template <int L, int NT>
+__device__ __forceinline__ void ar_load(float2* __restrict__ s, const float* __restrict__ src, int W, int wide, int tid) {
+    constexpr int Q = L / 4, RS = L / 2 + 1;
+    for (int t = tid; t < L * Q; t += NT) {
+        const int q = t % Q, y = t / Q;
+        const float* p = src + (int64_t)y * W + 4 * q;
+        f32x4 v;
+        if (wide) {
+            v = *(const f32x4*)p;
+        } else {
+            v.x = p[0], v.y = p[1], v.z = p[2], v.w = p[3];
+        }
+        float2* d = s + y * RS + 2 * q;
+        d[0] = make_float2(v.x, v.y);
+        d[1] = make_float2(v.z, v.w);
+    }
+    __syncthreads();
+}
+
+template <int L>
+__device__ __forceinline__ void ar_forward(float2* __restrict__ s, const float2* __restrict__ tw, int tid) {
+    constexpr int NT = psd_threads(L), NH = L / 2, RS = NH + 1;
+    fft_dif<NH, L, 1, RS, NT>(s, tw, tid);
+    real_split_nyquist<L, L, RS, NT>(s, tw, tid);
+    fft_dif<L, NH + 1, RS, 1, NT>(s, tw, tid);
+}
+
+template <int L>
+__global__ __launch_bounds__(psd_threads(L)) void spectral_ar_kernel(ArGeom g) {
+    constexpr int NT = psd_threads(L), NH = L / 2, RS = NH + 1, TOTAL = L * RS, NS = ar_state(L);
+    extern __shared__ __attribute__((aligned(16))) unsigned char psd_smem[];
+    float2* s = (float2*)psd_smem;      // [L][RS]
+    float2* tw = s + TOTAL;             // [PSD_TW]
+    float* s_rho = (float*)(tw + PSD_TW);  // [L]
+    float* s_gain = s_rho + L;          // [L]: sqrt(1 - rho^2)
+    float* s_wy = s_gain + L;           // [L]: this window's blend weights down the rows ...
+    float* s_wx = s_wy + L;             // [L]: ... and along them
+    const int tid = threadIdx.x;
+    const int per_plane = g.wins_y * g.wins_x;
+    const int64_t n = blockIdx.x / per_plane;  // plane * M + member
+    const int wi = (int)(blockIdx.x - n * per_plane);
+    const int wy = wi / g.wins_x, wx = wi - wy * g.wins_x;
+    const int y0 = wy * L + g.cy * NH, x0 = wx * L + g.cx * NH;  // y0 + L <= H, x0 + L <= W
+    const int64_t p = n / g.M;
+    for (int i = tid; i < PSD_TW; i += NT) {
+        double sn, cs;
+        sincospi(-(double)i / 256.0, &sn, &cs);
+        tw[i] = make_float2((float)cs, (float)sn);
+    }
+    for (int i = tid; i < L; i += NT) {
+        const float r = g.rho[i];
+        s_rho[i] = r;
+        s_gain[i] = (float)sqrt(fmax(fma(-(double)r, (double)r, 1.0), 0.0));
+        // offset class: h(i) = sin^2(pi (i + 1/2) / L); aligned class: 1 - h of the offset window that covers the pixel, 1 in the
+        // outer L / 2 of the frame where there is none
+        const double sh = sinpi(((double)i + 0.5) / (double)L), sc = sinpi(((double)((i + NH) % L) + 0.5) / (double)L);
+        const float h_own = (float)(sh * sh), h_other = (float)(sc * sc);
+        const int Y = y0 + i, X = x0 + i;
+        s_wy[i] = g.cy ? h_own : (Y < NH || Y >= g.H - NH) ? 1.f : 1.f - h_other;
+        s_wx[i] = g.cx ? h_own : (X < NH || X >= g.W - NH) ? 1.f : 1.f - h_other;
+    }
+    __syncthreads();
+    const int64_t origin = (int64_t)y0 * g.W + x0;
+    ar_load<L, NT>(s, g.z0 + p * g.z0_plane_stride + origin, g.W, g.wide_in, tid);
+    ar_forward<L>(s, tw, tid);
+    float2 X[NS];
+    float rho[NS], amp[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        X[j] = make_float2(0.f, 0.f);
+        rho[j] = 0.f, amp[j] = 0.f;
+        if (e < TOTAL) {
+            const int row = e / RS, c = e - row * RS;
+            int ky = brev<ilog2(L)>(row);
+            ky = ky >= NH ? ky - L : ky;
+            const int kx = c < NH ? brev<ilog2(NH)>(c) : NH;
+            const int d2 = kx * kx + ky * ky;
+            const int k = isqrt_floor(d2);
+            const int r = d2 <= k * (k + 1) ? k : k + 1;  // r (r - 1) < d2 <= r (r + 1); r <= L / sqrt(2) + 1 < L
+            X[j] = s[e];
+            rho[j] = s_rho[r];
+            amp[j] = s_gain[r] * (sqrtf(X[j].x * X[j].x + X[j].y * X[j].y) * (1.f / (float)L));
+        }
+    }
+    const float* wh = g.white + n * g.white_member_stride + origin;
+    float* out = g.out + n * g.out_member_stride + origin;
+    constexpr float INV = 1.f / ((float)L * (float)L);
+    for (int t = 0; t < g.T; ++t) {
+        __syncthreads();  // the reads of the step before (or of the state) are done
+        ar_load<L, NT>(s, wh + (int64_t)t * g.white_step_stride, g.W, g.wide_in, tid);
+        ar_forward<L>(s, tw, tid);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int e = tid + j * NT;
+            if (e < TOTAL) {
+                const float2 v = s[e];
+                X[j] = make_float2(fmaf(rho[j], X[j].x, amp[j] * v.x), fmaf(rho[j], X[j].y, amp[j] * v.y));
+                s[e] = X[j];
+            }
+        }
+        __syncthreads();
+        fft_dit_inverse<L, NH + 1, RS, 1, NT>(s, tw, tid);
+        real_merge<L, L, RS, NT>(s, tw, tid);
+        fft_dit_inverse<NH, L, 1, RS, NT>(s, tw, tid);
+        float* o = out + (int64_t)t * g.out_step_stride;
+        const bool first = g.cy == 0 && g.cx == 0;
+        for (int i = tid; i < L * (L / 4); i += NT) {
+            const int q = i % (L / 4), y = i / (L / 4);
+            const float2 a = s[y * RS + 2 * q], b = s[y * RS + 2 * q + 1];
+            const float wrow = s_wy[y];
+            const float w0 = wrow * s_wx[4 * q], w1 = wrow * s_wx[4 * q + 1], w2 = wrow * s_wx[4 * q + 2], w3 = wrow * s_wx[4 * q + 3];
+            float* d = o + (int64_t)y * g.W + 4 * q;
+            f32x4 v;
+            if (first) {
+                v.x = (a.x * INV) * w0, v.y = (a.y * INV) * w1, v.z = (b.x * INV) * w2, v.w = (b.y * INV) * w3;
+            } else {
+                if (g.wide_out) {
+                    v = *(const f32x4*)d;
+                } else {
+                    v.x = d[0], v.y = d[1], v.z = d[2], v.w = d[3];
+                }
+                v.x = fmaf(a.x * INV, w0, v.x), v.y = fmaf(a.y * INV, w1, v.y), v.z = fmaf(b.x * INV, w2, v.z), v.w = fmaf(b.y * INV, w3, v.w);
+            }
+            if (g.wide_out) {
+                *(f32x4*)d = v;
+            } else {
+                d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+            }
+        }
+    }
+}
+
+template <int L>
+int ar_run(const ArGeom& g, int64_t blocks, hipStream_t st) {
+    hipLaunchKernelGGL(spectral_ar_kernel<L>, dim3((unsigned)blocks), dim3(psd_threads(L)), ar_lds<L>(), st, g);
+    return 0;
+}
+
+template <int L>
+int ar_allow_lds() {
+    if (ar_lds<L>() <= 64 * 1024) return 0;
+    if (hipFuncSetAttribute((const void*)spectral_ar_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, ar_lds<L>()) != hipSuccess) {
+        dgmr_set_error("dgmr_spectral_ar: %d bytes of LDS per workgroup were refused: %s", ar_lds<L>(), hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    return 0;
+}
+
 // ---- exceedance table ----------------------------------------------------------------------------------------------------------------
 constexpr int EXC_MAX_M = 32, EXC_MAX_K = 8, EXC_THREADS = 256, EXC_TARGET_BLOCKS = 4096;
 
@@ -454,6 +725,51 @@ extern "C" int dgmr_radial_psd(const float* x, int64_t plane_stride, int64_t N, 
                       : psd_run_two_pass<512>(g, nwin, per_round, tw, spec, part, power, missing, st);
     }
     if (rc != 0) return rc;
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const float* white, int64_t white_member_stride,
+                                int64_t white_step_stride, const float* rho, int P, int M, int T, int H, int W, int L, float* out,
+                                int64_t out_member_stride, int64_t out_step_stride, void* stream) {
+    const char* fn = "dgmr_spectral_ar";
+    DGMR_CHECK_ARG(L == 32 || L == 64 || L == 128, "%s: window L=%d is not one of 32, 64, 128", fn, L);
+    DGMR_CHECK_ARG(T >= 1 && T <= 64, "%s: T=%d lead times, 1 ... 64 are supported", fn, T);
+    DGMR_CHECK_ARG(P >= 1 && M >= 1 && (int64_t)P * M <= (1 << 24), "%s: P=%d planes of M=%d members are out of range", fn, P, M);
+    DGMR_CHECK_ARG(H > 0 && W > 0 && H % L == 0 && W % L == 0, "%s: H=%d and W=%d must be positive multiples of the window L=%d", fn, H, W, L);
+    DGMR_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(z0 && white && rho && out, "%s: null pointer", fn);
+    const int64_t N = (int64_t)P * M, plane = (int64_t)H * W, cap = INT64_MAX / 4 / (N * 64);
+    DGMR_CHECK_ARG(z0_plane_stride >= 0 && z0_plane_stride <= cap, "%s: z0_plane_stride=%lld out of range", fn, (long long)z0_plane_stride);
+    DGMR_CHECK_ARG((N == 1 || (white_member_stride >= plane && white_member_stride <= cap)) &&
+                       (T == 1 || (white_step_stride >= plane && white_step_stride <= cap)),
+                   "%s: white_member_stride=%lld and white_step_stride=%lld must be at least H * W = %lld", fn,
+                   (long long)white_member_stride, (long long)white_step_stride, (long long)plane);
+    DGMR_CHECK_ARG((N == 1 || (out_member_stride >= plane && out_member_stride <= cap)) &&
+                       (T == 1 || (out_step_stride >= plane && out_step_stride <= cap)),
+                   "%s: out_member_stride=%lld and out_step_stride=%lld must be at least H * W = %lld", fn, (long long)out_member_stride,
+                   (long long)out_step_stride, (long long)plane);
+    DGMR_CHECK_ARG(N * (H / L) * (W / L) <= (1 << 30), "%s: %lld windows are out of range", fn, (long long)(N * (H / L) * (W / L)));
+    const int64_t wms = N == 1 ? 0 : white_member_stride, wss = T == 1 ? 0 : white_step_stride;
+    const int64_t oms = N == 1 ? 0 : out_member_stride, oss = T == 1 ? 0 : out_step_stride;
+    const int wide_in = (((uintptr_t)z0 | (uintptr_t)white) & 15) == 0 && z0_plane_stride % 4 == 0 && wms % 4 == 0 && wss % 4 == 0;
+    const int wide_out = ((uintptr_t)out & 15) == 0 && oms % 4 == 0 && oss % 4 == 0;
+    const int rc = L == 32 ? ar_allow_lds<32>() : L == 64 ? ar_allow_lds<64>() : ar_allow_lds<128>();
+    if (rc != 0) return rc;
+    hipStream_t st = ST;
+    for (int c = 0; c < 4; ++c) {  // (0,0) stores; (0,1), (1,0), (1,1) add, in this order
+        const int cy = c >> 1, cx = c & 1;
+        const int wins_y = H / L - cy, wins_x = W / L - cx;
+        if (wins_y == 0 || wins_x == 0) continue;
+        const ArGeom g{z0, white, rho, out, z0_plane_stride, wms, wss, oms, oss, M, T, H, W, cy, cx, wins_y, wins_x, wide_in, wide_out};
+        const int64_t blocks = N * wins_y * wins_x;
+        if (L == 32)
+            ar_run<32>(g, blocks, st);
+        else if (L == 64)
+            ar_run<64>(g, blocks, st);
+        else
+            ar_run<128>(g, blocks, st);
+    }
     DGMR_CHECK_LAUNCH();
     return 0;
 }

@@ -1,0 +1,151 @@
+"""Device time of the stochastic advection ensemble on a full 1536 x 1280 composite (skillful_nowcasting_amd/stochastic.py;
+dgmr_spectral_ar in csrc/spectrum.hip, dgmr_advect_series in csrc/advect.hip).
+
+    python tools/stochastic_timing.py [--repeats 7] [--out profiles/stochastic_timing.json]
+
+Inputs: the rain-covered sequence of tools/advection_timing.py (a smooth field moving by (2, -3) pixels per frame), M = 8 members,
+T = 18 lead times, window 128, the library's default lifetimes.  HIP events bracket single calls on one stream; after a warm-up the
+median over --repeats calls counts (minimum and maximum are listed).
+
+  * dgmr_spectral_ar alone (four launches), with the bytes it must move (white read once, out written by the first class and read
+    and written by the other three) and its transform count;
+  * the same recursion written with torch.fft (rfft2 / irfft2 over the windows of each class, the blend as slice updates) on the
+    same device, for scale, and how far the two results are apart;
+  * dgmr_advect_series for the M planes of T sources;
+  * one whole EnsembleAdvectionNowcaster.nowcast (conversion, motion, dB, noise drawn on the device, recursion, advection, back).
+Numbers are recorded, not asserted."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+H, W, T_OUT, MEMBERS, WINDOW = 1536, 1280, 18, 8, 128
+COPY_BYTES_PER_S = 6.29e12  # measured device-to-device copy rate of the MI355X
+
+
+def timed(fn, repeats):
+    import torch
+
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        times.append(t0.elapsed_time(t1))
+    return {"ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "calls": len(times)}
+
+
+def spectral_ar_torch(z0, white, rho, window):
+    """stochastic.spectral_ar_reference with torch.fft in fp32 on the tensors' device (half spectra: the fields are real)."""
+    import numpy as np
+    import torch
+
+    from skillful_nowcasting_amd.spectra import _radial_bins
+    from skillful_nowcasting_amd.stochastic import axis_weights
+
+    p, m, steps, h, w = white.shape
+    dev = z0.device
+    bins = torch.from_numpy(_radial_bins(window)[:, :window // 2 + 1].copy()).to(dev)
+    rk = rho[bins]
+    gain = torch.sqrt((1.0 - rk.double() ** 2).clamp_min(0.0)).float()
+    (ay, hy), (ax, hx) = axis_weights(h, window), axis_weights(w, window)
+    out = torch.zeros((p, m, steps, h, w), dtype=torch.float32, device=dev)
+    half = window // 2
+    for cy in (0, 1):
+        for cx in (0, 1):
+            ny, nx = h // window - cy, w // window - cx
+            if ny == 0 or nx == 0:
+                continue
+            ys, xs = slice(cy * half, cy * half + ny * window), slice(cx * half, cx * half + nx * window)
+            wgt = torch.from_numpy(np.outer((hy if cy else ay)[ys], (hx if cx else ax)[xs])).to(dev)
+
+            def windows(x):
+                t = x[..., ys, xs]
+                return t.reshape(x.shape[:-2] + (ny, window, nx, window)).movedim(-3, -2)
+
+            u = torch.fft.rfft2(windows(z0))[:, None]
+            amp = gain * (u.abs() / window)
+            state = u.expand(p, m, ny, nx, window, half + 1).clone()
+            for t in range(steps):
+                state = rk * state + amp * torch.fft.rfft2(windows(white[:, :, t]))
+                x = torch.fft.irfft2(state, s=(window, window)).movedim(-2, -3).reshape(p, m, ny * window, nx * window)
+                out[:, :, t, ys, xs] += x * wgt
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+
+    import __graft_entry__ as g
+
+    g.build()
+    from advection_timing import rain_sequence
+    from skillful_nowcasting_amd.advection import advect_series, lattice_geometry, motion_field
+    from skillful_nowcasting_amd.stochastic import EnsembleAdvectionNowcaster, lifetime_rho, spectral_ar, to_db
+
+    assert torch.cuda.is_available(), "needs a HIP device"
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    seq = rain_sequence(gen, dev, 4, (2, -3), False)  # [4, H, W]
+    rec = {"device": torch.cuda.get_device_name(0), "command": f"python tools/stochastic_timing.py --repeats {a.repeats}", "frame": [H, W],
+           "members": MEMBERS, "lead_times": T_OUT, "window": WINDOW, "assumed_rates": {"copy_bytes_per_s": COPY_BYTES_PER_S},
+           "wet_pixel_share": float((seq > 0).double().mean())}
+    nowcaster = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW)
+    rho = lifetime_rho(WINDOW).to(dev)
+    z0 = to_db(seq[-1:])
+    white = nowcaster.white_noise(1, MEMBERS, H, W, dev, seed=0)
+    out = torch.empty_like(white)
+    plane = MEMBERS * T_OUT * H * W * 4
+    windows = MEMBERS * sum((H // WINDOW - cy) * (W // WINDOW - cx) for cy in (0, 1) for cx in (0, 1))
+    ar = timed(lambda: spectral_ar(z0, white, rho, WINDOW, out=out), a.repeats)
+    # per class and covered pixel: white read once, out written (class (0,0)) or read and written (the other three)
+    share = {(cy, cx): (H // WINDOW - cy) * (W // WINDOW - cx) / ((H // WINDOW) * (W // WINDOW)) for cy in (0, 1) for cx in (0, 1)}
+    nbytes = int(plane * sum(f * (2 if c == (0, 0) else 3) for c, f in share.items()))
+    ar.update({"windows": windows, "transforms_2d": windows * (2 * T_OUT + 1), "bytes_moved": nbytes, "GB_per_s": nbytes / ar["ms"] / 1e6,
+               "ms_at_copy_rate": nbytes / COPY_BYTES_PER_S * 1e3})
+    rec["spectral_ar"] = ar
+    print(f"spectral_ar  M={MEMBERS} T={T_OUT} L={WINDOW}: {ar['ms']:.3f} ms ({ar['min_ms']:.3f} - {ar['max_ms']:.3f}), {windows} windows, "
+          f"{ar['GB_per_s']:.0f} GB/s of its own traffic", flush=True)
+    try:
+        ref = spectral_ar_torch(z0, white, rho, WINDOW)
+        gap = float((ref - out).abs().max())
+        tf = timed(lambda: spectral_ar_torch(z0, white, rho, WINDOW), max(3, a.repeats // 2))
+        tf["max_abs_difference_to_kernel"] = gap
+        tf["over_kernel"] = tf["ms"] / ar["ms"]
+        rec["spectral_ar_torch_fft"] = tf
+        print(f"torch.fft recursion: {tf['ms']:.3f} ms ({tf['over_kernel']:.1f} x the kernel), largest difference {gap:.3e}", flush=True)
+        del ref
+    except RuntimeError as e:  # no FFT library on the device
+        rec["spectral_ar_torch_fft"] = {"unavailable": str(e).splitlines()[0]}
+        print(f"torch.fft on the device is not available: {rec['spectral_ar_torch_fft']['unavailable']}", flush=True)
+    field = motion_field(seq[:, None], 32, 16, 8)
+    origin, spacing = lattice_geometry(32, 16)
+    moved = torch.empty(MEMBERS, T_OUT, H, W, device=dev)
+    adv = timed(lambda: advect_series(out[0], field, origin, spacing, field_group=MEMBERS, out=moved), a.repeats)
+    adv.update({"bytes_stored": plane, "GB_per_s_stored": plane / adv["ms"] / 1e6, "ms_at_copy_rate": 2 * plane / COPY_BYTES_PER_S * 1e3})
+    rec["advect_series"] = adv
+    print(f"advect_series {MEMBERS} x {T_OUT} planes: {adv['ms']:.3f} ms ({adv['GB_per_s_stored']:.0f} GB/s stored)", flush=True)
+    del moved, out, white
+    frames = seq[..., None].contiguous()
+    rec["nowcast"] = timed(lambda: nowcaster.nowcast(frames, MEMBERS, seed=1), a.repeats)
+    print(f"whole nowcast: {rec['nowcast']['ms']:.3f} ms", flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
