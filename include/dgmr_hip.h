@@ -738,6 +738,36 @@ int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_t x_step_st
                        int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Probability matching for the stochastic ensemble (stochastic.py: probability_match; csrc/probmatch.hip).  New symbols, same ABI
+ * version.
+ * z: the dB fields of dgmr_spectral_ar with its plane addressing - plane n = p M + m of lead time t at z + n member_stride +
+ * (t - 1) step_stride, H W contiguous fp32 values; out likewise with its two strides.  target_sorted: per case p the N = H W values of
+ * the frame to match, sorted ascending, at target_sorted + p target_stride.  mask: null, or uint8 planes at mask + p mask_plane_stride
+ * + (t - 1) mask_step_stride (0: one plane for all lead times); nonzero = rain is allowed here.  4096 bins of 1 / scale dB from lo;
+ * scale must be a power of two.  Per plane, every fp32 operation rounded once and none contracted:
+ *   u = (z - lo) * scale;  !(u >= 0) (below the range, NaN): b = 0, f = 0;  u >= 4096: b = 4095, f = 0;  else b = floor(u), f = u - b;
+ *   a masked-out element: b = 0, f = 0;
+ *   h[b] = the number of the plane's N elements in bin b;  c[b] = sum of h[b'] over b' < b;
+ *   r = c[b] + min(int(f * float(h[b])), h[b] - 1);  out = target_sorted[r], and 0.0 for a masked-out element.
+ * r lies in [c[b], c[b] + h[b] - 1], inside [0, N): the map is monotone in z, every output is a value of the target, and a rank is off
+ * from the exact one by less than its bin's occupancy.  All counts are integers (an LDS histogram per workgroup, its nonzero bins added
+ * with integer atomics onto the workspace, which the call clears first), so the result is the reference's bit for bit and two calls
+ * give the same bits.  A bin whose span of ranks reads one and the same target value - most of a radar frame is exact zeros - takes
+ * that value without reading the target per element (not where the case's target holds a -0.0 or a NaN, whose bits equal values do
+ * not fix).  out may be z itself (each element is read and written by the same lane); any other overlap is undefined.
+ * workspace: dgmr_probability_match_workspace(P, M, T) bytes - two rows of 4096 int32 per plane and a flag per case, 32768 P M T +
+ * 4 P rounded up to 16 -, 16-byte aligned (< 0 for P, M < 1, T outside 1 ... 64 or more than 2^20 planes).  16-byte accesses when z, out, the mask and all their strides allow them, 4-byte ones otherwise: no
+ * alignment demands.  Argument errors (null z, target_sorted, workspace or out, scale no power of two, lo not finite, H W > 2^24, a
+ * stride below H W - mask_step_stride may be 0 -, T outside 1 ... 64, a workspace that is too small) return < 0 and set
+ * dgmr_last_error() before anything is enqueued.  Runs on `stream`, does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgmr_probability_match_workspace(int P, int M, int T);
+int dgmr_probability_match(const float* z, int64_t member_stride, int64_t step_stride, const float* target_sorted, int64_t target_stride,
+                           const uint8_t* mask, int64_t mask_plane_stride, int64_t mask_step_stride, int P, int M, int T, int H, int W,
+                           float lo, float scale, void* workspace, int64_t workspace_bytes, float* out, int64_t out_member_stride,
+                           int64_t out_step_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py's roofline leg; not part of the reference's surface).  When enabled, every conv /
  * wgrad launch is bracketed by HIP events on its launch stream; collect() returns, per tile variant, the summed
  * kernel time, the summed algorithmic FLOPs (2*M*K*Cout) and the launch count, then clears the records.

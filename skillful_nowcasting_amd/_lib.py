@@ -161,6 +161,7 @@ SIGNATURES = {
     "dgmr_advect": [P, L, P, L, L, i, i, i, i, f, f, i, P, L, L, P],
     "dgmr_spectral_ar": [P, L, P, L, L, P, i, i, i, i, i, i, P, L, L, P],
     "dgmr_advect_series": [P, L, L, P, L, i, L, i, i, i, i, f, f, i, P, L, L, P],
+    "dgmr_probability_match": [P, L, L, P, L, P, L, L, i, i, i, i, i, f, f, P, L, P, L, L, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],
     "dgmr_pool2_phase_weights": [P, P, i, i, P],
     "dgmr_upsample_wgrad_sums": [P, P, i, i, i, i, P],
@@ -190,7 +191,8 @@ del i, f, L
 # buffer sizes: these return int64_t
 SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_grid_cell_acc_doubles": [c_int64],
                   "dgmr_ensemble_scores_workspace": [c_int, c_int64, c_int, c_int],
-                  "dgmr_radial_psd_workspace": [c_int64, c_int, c_int, c_int]}
+                  "dgmr_radial_psd_workspace": [c_int64, c_int, c_int, c_int],
+                  "dgmr_probability_match_workspace": [c_int, c_int, c_int]}
 
 _lib = None
 

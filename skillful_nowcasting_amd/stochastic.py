@@ -6,16 +6,25 @@
     bins) and whose noise is shaped by the window's own amplitude spectrum `A = |fft2(window)| / L` (the short-space idea of pysteps'
     SSFT generator): with unit white noise the expected power of every mode stays what the observation had, at every lead time;
   * the windows blended with sin^2 weights that sum to one (`spectral_ar`);
+  * optionally (`probability_matching=True`) every member and lead time pulled back to the marginal distribution of the last
+    observed frame (`probability_match`: the recursion keeps a window's spectrum, not its distribution - noise turns a field that
+    is mostly exact zeros into a roughly Gaussian one, with almost twice the observed wet area and a quarter of its heavy rain),
+    and rain kept to a dilated copy of the observed wet set (`precipitation_mask`: noise is shaped per window and spreads to the
+    far side of one);
   * the evolved fields moved along the motion field of the context (`advection.motion_field`, `advection.advect_series`: Lagrangian
     coordinates first, advection last) and taken back to rain rates (`from_db`).
 
 `spectral_ar_reference` is the specification in float64 numpy.  On a HIP device `spectral_ar` is `dgmr_spectral_ar`
 (csrc/spectrum.hip) on the current stream, without synchronisation; CPU tensors go through the reference.
+`probability_match_reference` is the specification of the matching in fp32 numpy, which `dgmr_probability_match`
+(csrc/probmatch.hip) reproduces bit for bit: ranks from a 4096-bin histogram of each plane instead of a sort.
 
-Limits: no probability matching (the marginal distribution of the members is not pulled back to the observed one), no
-precipitation mask (noise can create light rain just outside an echo), no velocity perturbations, and the lifetime law is a fixed
-power law, not estimated from data.  The white field and the result each take M T H W floats: about 1.1 GB each for 8 members and 18
-lead times of a 1536 x 1280 frame.
+Matching and mask act in Lagrangian coordinates: the bilinear advection afterwards blurs the wet / dry edge over a pixel, as it does
+for the deterministic baseline, so a moved member's distribution is the observed one only up to that interpolation.
+
+Limits: no velocity perturbations, and the lifetime law is a fixed power law, not estimated from data; the mask's dilation law is
+fixed as well (radius + growth t), it does not follow the members.  The white field and the result each take M T H W floats: about
+1.1 GB each for 8 members and 18 lead times of a 1536 x 1280 frame.
 """
 from __future__ import annotations
 
@@ -28,6 +37,7 @@ from .advection import CONTEXT_FRAMES, MAX_STEPS, AdvectionNowcaster, _planes, _
 from .spectra import _radial_bins
 
 WINDOWS = (32, 64, 128)
+PM_BINS = 4096  # bins of `probability_match`: with its defaults [-64, 64) dB in steps of 1/32 dB
 
 
 def _check_window(window) -> int:
@@ -205,16 +215,165 @@ def spectral_ar(z0: torch.Tensor, white: torch.Tensor, rho: torch.Tensor, window
     return out
 
 
+# ---- probability matching and the precipitation mask -----------------------------------------------------------------------------------
+def _check_bins(lo: float, scale: float):
+    lo, scale = float(lo), float(scale)
+    if not (np.isfinite(lo) and np.isfinite(scale) and scale > 0 and np.frexp(scale)[0] == 0.5 and np.float32(scale) == scale):
+        raise ValueError(f"lo={lo} must be finite and scale={scale} a power of two")
+    return np.float32(lo), np.float32(scale)
+
+
+def probability_match_reference(z, target_sorted, mask=None, lo: float = -64.0, scale: float = 32.0) -> np.ndarray:
+    """The specification of `dgmr_probability_match`, in fp32 numpy -> fp32 [P, M, T, H, W]; the device reproduces it bit for bit.
+
+    z: fp32 [P, M, T, H, W], dB fields in Lagrangian coordinates (`spectral_ar`'s output); target_sorted: fp32 [P, H W], per case the
+    frame to match (the last observed dB frame, dry zeros included: matching over the whole plane restores the wet-area ratio too)
+    sorted ascending; mask: None or uint8 [P, 1 or T, H, W], nonzero where rain is allowed.  PM_BINS = 4096 bins of 1 / scale dB from
+    lo, scale a power of two; N = H W <= 2^24.  Per plane (p, m, t), every operation an fp32 operation rounded once:
+      u = (z - lo) scale;  !(u >= 0) (below the range, NaN): b = 0, f = 0;  u >= 4096: b = 4095, f = 0;  else b = floor(u), f = u - b
+      (exact);  a masked-out element: b = 0, f = 0;
+      h[b] counts the plane's N elements, c[b] = sum of h[b'] over b' < b;
+      r = c[b] + min(int(f float(h[b])), h[b] - 1);  out = target_sorted[p][r], and 0.0 for a masked-out element.
+    r lies in [c[b], c[b] + h[b] - 1]: the map is monotone in z, every output is a value of the target, a rank differs from the exact
+    one by less than its bin's occupancy, and all exact zeros of a member (entirely dry windows) share one rank."""
+    lo32, scale32 = _check_bins(lo, scale)
+    z = np.asarray(z, dtype=np.float32)
+    target_sorted = np.asarray(target_sorted, dtype=np.float32)
+    if z.ndim != 5 or target_sorted.ndim != 2 or target_sorted.shape != (z.shape[0], z.shape[3] * z.shape[4]):
+        raise ValueError(f"z must be [P, M, T, H, W] and target_sorted [P, H W], got {z.shape} and {target_sorted.shape}")
+    p, m, steps, h, w = z.shape
+    n = h * w
+    if not 1 <= steps <= MAX_STEPS or m < 1 or p < 1 or not 1 <= n <= 1 << 24:
+        raise ValueError(f"T={steps} must be 1 ... {MAX_STEPS}, P={p} and M={m} at least 1, H W = {n} 1 ... 2^24")
+    allowed = None
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.dtype != np.uint8 or mask.ndim != 4 or mask.shape[0] != p or mask.shape[1] not in (1, steps) or mask.shape[2:] != (h, w):
+            raise ValueError(f"mask must be uint8 [{p}, 1 or {steps}, {h}, {w}], got {mask.dtype} {mask.shape}")
+        allowed = np.broadcast_to((mask != 0)[:, None], z.shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = (z - lo32) * scale32
+        inside = (u >= 0) & (u < PM_BINS)
+        top = u >= PM_BINS
+    if allowed is not None:
+        inside, top = inside & allowed, top & allowed
+    fl = np.floor(np.where(inside, u, np.float32(0)))  # fp32
+    b = np.where(top, PM_BINS - 1, fl.astype(np.int64))
+    f = np.where(inside, u, np.float32(0)) - fl
+    assert u.dtype == f.dtype == np.float32
+    planes = p * m * steps
+    b = b.reshape(planes, n)
+    hist = np.bincount((b + np.arange(planes)[:, None] * PM_BINS).ravel(), minlength=planes * PM_BINS).reshape(planes, PM_BINS)
+    before = np.cumsum(hist, axis=1) - hist
+    hb = np.take_along_axis(hist, b, axis=1)
+    within = (f.reshape(planes, n) * hb.astype(np.float32)).astype(np.int64)
+    rank = np.take_along_axis(before, b, axis=1) + np.minimum(within, hb - 1)
+    case = np.repeat(np.arange(p), m * steps)[:, None]
+    out = target_sorted[case, rank].reshape(z.shape)
+    if allowed is not None:
+        out = np.where(allowed, out, np.float32(0))
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def probability_match(z: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, lo: float = -64.0, scale: float = 32.0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`probability_match_reference` for torch tensors -> fp32 [P, M, T, H, W] on the inputs' device: every plane of z takes the
+    marginal distribution of its case's `target` plane, through binned ranks.
+
+    z: fp32 [P, M, T, H, W]; target: fp32 [P, H, W], sorted here once per case (`torch.sort`: P planes); mask: None or uint8
+    [P, 1 or T, H, W] (`precipitation_mask`).  The layouts of z and out are `spectral_ar`'s: contiguous planes, steps at least H W
+    apart, the (P, M) pairs one stride apart; a z of another layout is copied, an out of another layout is refused.  out may be z (in
+    place).  On a HIP device one `dgmr_probability_match` on the current stream, nothing synchronised; on the CPU the reference."""
+    _check_bins(lo, scale)
+    if z.dim() != 5 or z.dtype != torch.float32:
+        raise ValueError(f"z must be a float32 [P, M, T, H, W] tensor, got {z.dtype} {tuple(z.shape)}")
+    p, m, steps, h, w = (int(v) for v in z.shape)
+    n = h * w
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if m < 1 or p < 1 or not 1 <= n <= 1 << 24:
+        raise ValueError(f"P={p} planes and M={m} members: at least one each is required, and H W = {n} must be 1 ... 2^24")
+    if tuple(target.shape) != (p, h, w) or target.dtype != torch.float32 or target.device != z.device:
+        raise ValueError(f"target must be a float32 [{p}, {h}, {w}] tensor on {z.device}, got {target.dtype} {tuple(target.shape)} on "
+                         f"{target.device}")
+    if mask is not None and (mask.dim() != 4 or mask.dtype != torch.uint8 or mask.device != z.device or mask.shape[0] != p
+                             or mask.shape[1] not in (1, steps) or tuple(mask.shape[2:]) != (h, w)):
+        raise ValueError(f"mask must be a uint8 [{p}, 1 or {steps}, {h}, {w}] tensor on {z.device}, got {mask.dtype} {tuple(mask.shape)} on "
+                         f"{mask.device}")
+    if out is None:
+        out = torch.empty((p, m, steps, h, w), dtype=torch.float32, device=z.device)
+    elif tuple(out.shape) != (p, m, steps, h, w) or out.dtype != torch.float32 or out.device != z.device or _members_layout(out) is None:
+        raise ValueError(f"out must be a float32 [{p}, {m}, {steps}, {h}, {w}] tensor on {z.device} with contiguous planes and its "
+                         "(P, M) pairs one stride apart")
+    target_sorted = torch.sort(target.reshape(p, n), dim=1).values
+    if not z.is_cuda:
+        ref = probability_match_reference(z.numpy(), target_sorted.numpy(), None if mask is None else mask.numpy(), lo, scale)
+        out.copy_(torch.from_numpy(ref))
+        return out
+    from ._lib import call, load
+
+    if _members_layout(z) is None:
+        z = z.contiguous()
+    zms, zss = _members_layout(z)
+    oms, oss = _members_layout(out)
+    mask_ptr = mask_ps = mask_ss = 0
+    if mask is not None:
+        mask = mask.contiguous()
+        mask_ptr, mask_ps, mask_ss = mask.data_ptr(), int(mask.shape[1]) * n, n if mask.shape[1] > 1 else 0
+    device = z.device
+    with torch.cuda.device(device):
+        need = int(load().dgmr_probability_match_workspace(p, m, steps))
+        if need < 0:
+            raise ValueError(f"P M T = {p * m * steps} planes are out of range")
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        call("dgmr_probability_match", z.data_ptr(), zms, zss, target_sorted.data_ptr(), n, mask_ptr or None, mask_ps, mask_ss, p, m, steps,
+             h, w, float(lo), float(scale), workspace.data_ptr(), need, out.data_ptr(), oms, oss, _stream(device))
+    return out
+
+
+def precipitation_mask(z0: torch.Tensor, pad: float, radius: int, growth: float = 0.0, steps: int = 1) -> torch.Tensor:
+    """Where an ensemble member may rain -> uint8 [P, 1 or steps, H, W] on z0's device: the wet set `z0 >= pad` of the last observed
+    dB frame (fp32 [P, H, W]) dilated by a square of half-width radius + round(growth t) pixels at lead time t = 1 ... steps.
+    growth = 0 gives ONE plane for all lead times.  Unlike pysteps' incremental mask the law is fixed: it does not follow what the
+    members do.  torch (`max_pool2d`, one row and one column pass): it runs once per case and is not a hot path."""
+    if z0.dim() != 3 or z0.dtype != torch.float32:
+        raise ValueError(f"z0 must be a float32 [P, H, W] tensor, got {z0.dtype} {tuple(z0.shape)}")
+    radius, steps, growth = int(radius), int(steps), float(growth)
+    if radius < 0 or growth < 0 or not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"radius={radius} and growth={growth} must not be negative, steps={steps} must be 1 ... {MAX_STEPS}")
+    wet = (z0 >= pad).to(torch.float32)[:, None]
+    planes = []
+    for t in range(1, steps + 1) if growth > 0 else (1,):
+        k = radius + int(round(growth * t))
+        grown = wet
+        if k > 0:
+            grown = torch.nn.functional.max_pool2d(grown, (2 * k + 1, 1), stride=1, padding=(k, 0))
+            grown = torch.nn.functional.max_pool2d(grown, (1, 2 * k + 1), stride=1, padding=(0, k))
+        planes.append(grown)
+    return (torch.cat(planes, dim=1) > 0).to(torch.uint8)
+
+
 class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     """`AdvectionNowcaster` with `num_members` stochastic members: the last frame in dB evolves per window and Fourier mode by
     `spectral_ar` in Lagrangian coordinates, every member is then moved along the context's motion field (`advect_series`, the
     members of a case sharing its field) and taken back to rain rates.  window: L of `spectral_ar` (H and W must be multiples);
-    threshold, pad: `to_db`'s; rho: fp32 [window] lag-1 correlations per radial wavenumber, None for `lifetime_rho(window)`."""
+    threshold, pad: `to_db`'s; rho: fp32 [window] lag-1 correlations per radial wavenumber, None for `lifetime_rho(window)`.
+    probability_matching: match every member and lead time to the last observed dB frame (`probability_match`, in place, before the
+    advection); mask_radius (needs the matching): None for no mask, else `precipitation_mask`'s radius in pixels, mask_growth its
+    growth in pixels per lead time.  The defaults leave all three off."""
 
     def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
                  min_wet: Optional[int] = None, smooth: int = 2, window: int = 128, threshold: float = 0.1, pad: float = 5.0,
-                 rho: Optional[torch.Tensor] = None):
+                 rho: Optional[torch.Tensor] = None, probability_matching: bool = False, mask_radius: Optional[int] = None,
+                 mask_growth: float = 0.0):
         super().__init__(forecast_steps, block, stride, radius, wet_threshold, min_wet, smooth)
+        self.probability_matching = bool(probability_matching)
+        if mask_radius is not None and not self.probability_matching:
+            raise ValueError("mask_radius needs probability_matching=True: a masked-out element is dry only after the matching")
+        if (mask_radius is not None and int(mask_radius) < 0) or not mask_growth >= 0 or (mask_radius is None and mask_growth != 0):
+            raise ValueError(f"mask_radius={mask_radius} and mask_growth={mask_growth} must not be negative, and a growth needs a radius")
+        self.mask_radius = None if mask_radius is None else int(mask_radius)
+        self.mask_growth = float(mask_growth)
         self.window = _check_window(window)
         self.threshold, self.pad = float(threshold), float(pad)
         rho = lifetime_rho(self.window) if rho is None else torch.as_tensor(rho, dtype=torch.float32)
@@ -244,6 +403,11 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         origin, spacing = lattice_geometry(self.params["block"], self.params["stride"])
         z0 = to_db(context[-1], self.threshold, self.pad)
         z = spectral_ar(z0, white, self.rho.to(context.device), self.window)
+        if self.probability_matching:
+            mask = None
+            if self.mask_radius is not None:
+                mask = precipitation_mask(z0, self.pad, self.mask_radius, self.mask_growth, self.forecast_steps)
+            probability_match(z, z0, mask, out=z)
         moved = advect_series(z.view(planes * num_members, self.forecast_steps, h, w), self.last_field, origin, spacing,
                               field_group=num_members)
         return from_db(moved, self.threshold, self.pad).view(shape)

@@ -2,6 +2,7 @@
 dgmr_spectral_ar in csrc/spectrum.hip, dgmr_advect_series in csrc/advect.hip).
 
     python tools/stochastic_timing.py [--repeats 7] [--out profiles/stochastic_timing.json]
+                                      [--match-out profiles/probability_match_timing.json]
 
 Inputs: the rain-covered sequence of tools/advection_timing.py (a smooth field moving by (2, -3) pixels per frame), M = 8 members,
 T = 18 lead times, window 128, the library's default lifetimes.  HIP events bracket single calls on one stream; after a warm-up the
@@ -13,6 +14,12 @@ median over --repeats calls counts (minimum and maximum are listed).
     same device, for scale, and how far the two results are apart;
   * dgmr_advect_series for the M planes of T sources;
   * one whole EnsembleAdvectionNowcaster.nowcast (conversion, motion, dB, noise drawn on the device, recursion, advection, back).
+With --match-out also (dgmr_probability_match in csrc/probmatch.hip), written to that file:
+  * probability_match alone on the recursion's output (the target's sort and the workspace included), without and with a mask, with
+    the rate it reaches on two reads and one write of M T H W floats;
+  * the same ranks by a full sort on the device (argsort of every plane, the sorted target scattered through it), for scale, and
+    how much of the two results differs (a binned rank is off by less than a bin's occupancy; ties are ordered arbitrarily by a sort);
+  * the whole nowcast without matching, with it, and with it and a mask.
 Numbers are recorded, not asserted."""
 import argparse
 import json
@@ -81,10 +88,22 @@ def spectral_ar_torch(z0, white, rho, window):
     return out
 
 
+def rank_match_torch(z, target):
+    """Exact rank matching with torch: every plane sorted in full, the sorted target scattered through the order."""
+    import torch
+
+    p, m, steps, h, w = z.shape
+    order = z.reshape(p, m * steps, h * w).argsort(dim=2)
+    out = torch.empty((p, m * steps, h * w), dtype=torch.float32, device=z.device)
+    out.scatter_(2, order, torch.sort(target.reshape(p, 1, h * w), dim=2).values.expand(p, m * steps, h * w))
+    return out.view(z.shape)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--match-out", default=None)
     a = ap.parse_args()
     import torch
 
@@ -137,10 +156,43 @@ def main():
     adv.update({"bytes_stored": plane, "GB_per_s_stored": plane / adv["ms"] / 1e6, "ms_at_copy_rate": 2 * plane / COPY_BYTES_PER_S * 1e3})
     rec["advect_series"] = adv
     print(f"advect_series {MEMBERS} x {T_OUT} planes: {adv['ms']:.3f} ms ({adv['GB_per_s_stored']:.0f} GB/s stored)", flush=True)
-    del moved, out, white
+    del moved, white
+    match = None
+    if a.match_out:
+        from skillful_nowcasting_amd.stochastic import precipitation_mask, probability_match
+
+        match = {k: rec[k] for k in ("device", "frame", "members", "lead_times", "window", "wet_pixel_share")}
+        match["command"] = f"python tools/stochastic_timing.py --repeats {a.repeats} --match-out {a.match_out}"
+        matched = torch.empty_like(out)
+        for key, mask in (("probability_match", None), ("probability_match_masked", precipitation_mask(z0, 5.0, 8))):
+            pm = timed(lambda: probability_match(out, z0, mask, out=matched), a.repeats)
+            pm.update({"bytes_moved": 3 * plane, "GB_per_s": 3 * plane / pm["ms"] / 1e6, "ms_at_copy_rate": 3 * plane / COPY_BYTES_PER_S * 1e3})
+            match[key] = pm
+            print(f"{key} {MEMBERS} x {T_OUT} planes: {pm['ms']:.3f} ms ({pm['min_ms']:.3f} - {pm['max_ms']:.3f}), {pm['GB_per_s']:.0f} GB/s "
+                  "of two reads and a write", flush=True)
+        probability_match(out, z0, out=matched)
+        exact = rank_match_torch(out, z0)
+        ts = timed(lambda: rank_match_torch(out, z0), max(3, a.repeats // 2))
+        ts.update({"over_kernel": ts["ms"] / match["probability_match"]["ms"], "share_of_elements_that_differ": float((exact != matched).double().mean()),
+                   "max_abs_difference_dB": float((exact - matched).abs().max())})
+        match["rank_match_torch_sort"] = ts
+        print(f"torch argsort + scatter: {ts['ms']:.3f} ms ({ts['over_kernel']:.1f} x the kernel), {ts['share_of_elements_that_differ']:.2e} of "
+              f"the elements differ, by at most {ts['max_abs_difference_dB']:.3f} dB", flush=True)
+        del exact, matched
+    del out
     frames = seq[..., None].contiguous()
     rec["nowcast"] = timed(lambda: nowcaster.nowcast(frames, MEMBERS, seed=1), a.repeats)
     print(f"whole nowcast: {rec['nowcast']['ms']:.3f} ms", flush=True)
+    if match is not None:
+        match["nowcast"] = rec["nowcast"]
+        for key, kw in (("nowcast_matched", {}), ("nowcast_matched_masked", {"mask_radius": 8})):
+            nc = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW, probability_matching=True, **kw)
+            match[key] = timed(lambda: nc.nowcast(frames, MEMBERS, seed=1), a.repeats)
+            match[key]["over_unmatched"] = match[key]["ms"] / rec["nowcast"]["ms"]
+            print(f"whole {key}: {match[key]['ms']:.3f} ms ({match[key]['over_unmatched']:.2f} x the unmatched nowcast)", flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.match_out)), exist_ok=True)
+        with open(a.match_out, "w") as fh:
+            json.dump(match, fh, indent=1)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
