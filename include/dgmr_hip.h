@@ -738,6 +738,30 @@ int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_t x_step_st
                        int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lag spectra: the radially binned cross-spectrum of two planes over the windows and bins dgmr_spectral_ar evolves (stochastic.py:
+ * lag_spectra, estimate_rho; csrc/spectrum.hip).  New symbol, same ABI version.
+ * a, b: N fp32 planes [H][W] each, plane n at a + n a_plane_stride and b + n b_plane_stride (elements, >= H * W), any finite real
+ * values (no missing-value rule, as for z0 of dgmr_spectral_ar).  L one of 32, 64, 128; H and W multiples of L.  The windows are the
+ * four classes of dgmr_spectral_ar, origins (i L + cy L / 2, j L + cx L / 2), i < H / L - cy, j < W / L - cx, numbered per plane class
+ * by class in the order (0,0), (0,1), (1,0), (1,1) and row-major inside a class; Wn = the sum over the classes of
+ * (H / L - cy) (W / L - cx).  With A = fft2(a patch), B = fft2(b patch), unnormalised, over ALL L^2 modes of radial bin r:
+ *   sums[n][window][q][r]  double  q = 0: sum |A|^2;  q = 1: sum |B|^2;  q = 2: sum Re(A conj B);   [N][Wn][3][L]
+ * r is dgmr_spectral_ar's bin (r (r - 1) < kx^2 + ky^2 <= r (r + 1) over the signed frequencies in [-L/2, L/2); r < L): unlike
+ * dgmr_radial_psd the corner modes with r >= L / 2 and the Nyquist row and column are kept.  Bins that hold no mode (all above
+ * round(L / sqrt 2)) are written as 0.  fp32 radix-2 transforms on the half spectrum with the Nyquist column carried (the forward
+ * transform of dgmr_spectral_ar); a mode with 0 < kx < L / 2 counts twice, one with kx = 0 or kx = L / 2 once.  The three terms of a
+ * mode are formed in fp32 by one expression shape, fma(re, re', im im'), by one copy of the transform code, so b == a gives three
+ * bit-equal rows and b == -a gives q = 2 equal to -(q = 0); they are added in float64 in a fixed order (ascending kx and |ky|, +ky
+ * before -ky, four column partials per bin in index order).  One workgroup per (plane, window), one launch, no workspace, no
+ * floating-point atomics: two calls give the same bits and the result for plane n does not depend on N.  16-byte loads when both
+ * pointers and both strides allow them, 4-byte loads otherwise: no alignment demands on a and b (sums: 8 bytes).  Argument errors
+ * (null pointers, L outside the set, H or W not a multiple of L, N < 1, a plane stride below H * W) return < 0 and set
+ * dgmr_last_error() before anything is enqueued.  Runs on `stream`, does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_lag_spectra(const float* a, int64_t a_plane_stride, const float* b, int64_t b_plane_stride, int64_t N, int H, int W, int L,
+                     double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Probability matching for the stochastic ensemble (stochastic.py: probability_match; csrc/probmatch.hip).  New symbols, same ABI
  * version.
  * z: the dB fields of dgmr_spectral_ar with its plane addressing - plane n = p M + m of lead time t at z + n member_stride +

@@ -1,7 +1,8 @@
 // The two remaining verification plots on the device (spectra.py, value.py): the radially averaged power spectral density of L x L
 // windows (dgmr_radial_psd) and the exceedance table that reliability, Brier score, ROC points and economic value are derived from
 // (dgmr_exceedance_table).  And, built on the PSD's transforms, the AR(1) noise windows of the stochastic advection ensemble
-// (stochastic.py: dgmr_spectral_ar; its section below says how).
+// (stochastic.py: dgmr_spectral_ar; its section below says how) and, on the same windows and bins, the radially binned cross-spectrum
+// of two planes that the estimate of the recursion's rho(r) pools (dgmr_lag_spectra; its section too).
 //
 // PSD.  fp32 radix-2 decimation-in-frequency transforms in LDS (two stages per pass and barrier), twiddles from a table of exp(-2 pi i k / 512) computed in double and
 // rounded to fp32 (psd_twiddle_kernel writes it to the head of the workspace; every kernel copies it to LDS).  The input is real, so
@@ -623,6 +624,151 @@ int ar_allow_lds() {
     return 0;
 }
 
+// ---- lag spectra (stochastic.py: lag_spectra, estimate_rho) ----------------------------------------------------------------------------
+// One workgroup per (plane, window), the four window classes of the recursion in one launch.  The `b` patch is transformed first and
+// its half spectrum kept in registers (ar_state(L) elements per thread, as spectral_ar_kernel holds X), the `a` patch is transformed
+// in the same LDS buffer by the SAME code (one loop body, not unrolled: equal inputs give equal bits).  Every owned element is then
+// overwritten by its fp32 terms - (|A|^2, |B|^2) for a first walk over the bins, Re(A conj B) for a second - and the walk is
+// bin_modes' extended to r < L and to the Nyquist column: thread (r, j) adds the columns kx = j (mod 4) of bin r in ascending kx
+// and |ky| (+ky before -ky; ky = -L / 2 once), in float64 with the Hermitian weight (2 for 0 < kx < L / 2, 1 for kx = 0 and L / 2);
+// the four partials of a bin are added in j order through the transform buffer.  No atomics, no workspace.
+struct LagGeom {
+    const float* a;
+    const float* b;
+    double* sums;
+    int64_t a_plane_stride, b_plane_stride;
+    int H, W, wins_per_plane, wide;
+};
+
+template <int L>
+constexpr int lag_lds() { return L * (L / 2 + 1) * 8 + PSD_TW * 8; }  // 3 * 4 * L doubles of partials fit into the transform buffer
+
+// acc0, acc1: this thread's sums of the two components of s over the modes of bin tid % L in the columns kx = tid / L (mod 4)
+template <int L>
+__device__ __forceinline__ void lag_walk(const float2* __restrict__ s, int tid, double& acc0, double& acc1) {
+    constexpr int NH = L / 2, RS = NH + 1, P = psd_threads(L) / L;
+    const int r = tid % L, j = tid / L;
+    const int hi_all = r * (r + 1), lo_all = r == 0 ? -1 : r * (r - 1);
+    acc0 = 0.0, acc1 = 0.0;
+    for (int kx = j; kx <= NH; kx += P) {
+        const int hi = hi_all - kx * kx, lo = lo_all - kx * kx;
+        if (hi < 0) break;  // (kx only grows)
+        const int kmax = min(isqrt_floor(hi), NH);
+        const int kmin = lo < 0 ? 0 : isqrt_floor(lo) + 1;
+        const int col = kx < NH ? brev<ilog2(NH)>(kx) : NH;
+        double c0 = 0.0, c1 = 0.0;
+        for (int ky = kmin; ky <= kmax; ++ky) {
+            if (ky < NH) {
+                const float2 v = s[brev<ilog2(L)>(ky) * RS + col];
+                c0 += (double)v.x, c1 += (double)v.y;
+            }
+            if (ky > 0) {  // -ky, which for ky = L / 2 is the Nyquist row itself
+                const float2 u = s[brev<ilog2(L)>(L - ky) * RS + col];
+                c0 += (double)u.x, c1 += (double)u.y;
+            }
+        }
+        const bool twice = kx > 0 && kx < NH;
+        acc0 += twice ? 2.0 * c0 : c0;
+        acc1 += twice ? 2.0 * c1 : c1;
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(psd_threads(L)) void lag_spectra_kernel(LagGeom g) {
+    constexpr int NT = psd_threads(L), NH = L / 2, RS = NH + 1, TOTAL = L * RS, NS = ar_state(L), P = NT / L;
+    static_assert(3 * P * L * 8 <= TOTAL * 8 && 3 * L <= NT, "the partials live in the transform buffer, one thread per (q, r) adds them");
+    extern __shared__ __attribute__((aligned(16))) unsigned char psd_smem[];
+    float2* s = (float2*)psd_smem;  // [L][RS]
+    float2* tw = s + TOTAL;         // [PSD_TW]
+    const int tid = threadIdx.x;
+    const int64_t n = blockIdx.x / g.wins_per_plane;
+    int wi = (int)(blockIdx.x - n * g.wins_per_plane);
+    // the window's class: (0,0), (0,1), (1,0), (1,1), row-major inside a class
+    const int ny = g.H / L, nx = g.W / L;
+    int cy = 0, cx = 0;
+    for (int c = 0; c < 3; ++c) {
+        const int count = (ny - cy) * (nx - cx);
+        if (wi < count) break;
+        wi -= count;
+        cy = (c + 1) >> 1, cx = (c + 1) & 1;
+    }
+    const int wins_x = nx - cx;  // > 0: wi is inside this class
+    const int wy = wi / wins_x, wx = wi - wy * wins_x;
+    const int y0 = wy * L + cy * NH, x0 = wx * L + cx * NH;  // y0 + L <= H, x0 + L <= W
+    for (int i = tid; i < PSD_TW; i += NT) {
+        double sn, cs;
+        sincospi(-(double)i / 256.0, &sn, &cs);
+        tw[i] = make_float2((float)cs, (float)sn);
+    }
+    __syncthreads();
+    const int64_t origin = (int64_t)y0 * g.W + x0;
+    float2 B[NS];
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const float* src = pass == 0 ? g.b + n * g.b_plane_stride : g.a + n * g.a_plane_stride;
+        ar_load<L, NT>(s, src + origin, g.W, g.wide, tid);
+        ar_forward<L>(s, tw, tid);
+        if (pass == 0) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const int e = tid + j * NT;
+                B[j] = e < TOTAL ? s[e] : make_float2(0.f, 0.f);
+            }
+            __syncthreads();  // everyone holds its part of B before the buffer is loaded again
+        }
+    }
+    float cross[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        cross[j] = 0.f;
+        if (e < TOTAL) {
+            const float2 av = s[e], bv = B[j];
+            // one expression shape for the three terms: b == a gives three equal values, b == -a gives cross == -|A|^2
+            s[e] = make_float2(fmaf(av.x, av.x, av.y * av.y), fmaf(bv.x, bv.x, bv.y * bv.y));
+            cross[j] = fmaf(av.x, bv.x, av.y * bv.y);
+        }
+    }
+    __syncthreads();
+    double pa, pb, pc, unused;
+    lag_walk<L>(s, tid, pa, pb);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        if (e < TOTAL) s[e] = make_float2(cross[j], 0.f);
+    }
+    __syncthreads();
+    lag_walk<L>(s, tid, pc, unused);
+    __syncthreads();
+    double* part = (double*)psd_smem;  // [3][P][L]
+    {
+        const int r = tid % L, j = tid / L;
+        part[(0 * P + j) * L + r] = pa;
+        part[(1 * P + j) * L + r] = pb;
+        part[(2 * P + j) * L + r] = pc;
+    }
+    __syncthreads();
+    if (tid < 3 * L) {
+        const int q = tid / L, r = tid - q * L;
+        double v = part[(q * P) * L + r];
+#pragma unroll
+        for (int j = 1; j < P; ++j) v += part[(q * P + j) * L + r];
+        g.sums[((int64_t)blockIdx.x * 3 + q) * L + r] = v;
+    }
+}
+
+template <int L>
+int lag_run(const LagGeom& g, int64_t blocks, hipStream_t st) {
+    if (lag_lds<L>() > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)lag_spectra_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, lag_lds<L>()) != hipSuccess) {
+        dgmr_set_error("dgmr_lag_spectra: %d bytes of LDS per workgroup were refused: %s", lag_lds<L>(), hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    hipLaunchKernelGGL(lag_spectra_kernel<L>, dim3((unsigned)blocks), dim3(psd_threads(L)), lag_lds<L>(), st, g);
+    return 0;
+}
+
 // ---- exceedance table ----------------------------------------------------------------------------------------------------------------
 constexpr int EXC_MAX_M = 32, EXC_MAX_K = 8, EXC_THREADS = 256, EXC_TARGET_BLOCKS = 4096;
 
@@ -770,6 +916,31 @@ extern "C" int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const 
         else
             ar_run<128>(g, blocks, st);
     }
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_lag_spectra(const float* a, int64_t a_plane_stride, const float* b, int64_t b_plane_stride, int64_t N, int H, int W, int L,
+                                double* sums, void* stream) {
+    const char* fn = "dgmr_lag_spectra";
+    DGMR_CHECK_ARG(L == 32 || L == 64 || L == 128, "%s: window L=%d is not one of 32, 64, 128", fn, L);
+    DGMR_CHECK_ARG(N >= 1 && N <= (1 << 24), "%s: N=%lld planes out of range", fn, (long long)N);
+    DGMR_CHECK_ARG(H > 0 && W > 0 && H % L == 0 && W % L == 0, "%s: H=%d and W=%d must be positive multiples of the window L=%d", fn, H, W, L);
+    DGMR_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(a && b && sums, "%s: null pointer", fn);
+    DGMR_CHECK_ARG(((uintptr_t)sums & 7) == 0, "%s: sums must be 8-byte aligned", fn);
+    const int64_t plane = (int64_t)H * W, cap = INT64_MAX / 4 / N;
+    DGMR_CHECK_ARG(a_plane_stride >= plane && a_plane_stride <= cap && b_plane_stride >= plane && b_plane_stride <= cap,
+                   "%s: a_plane_stride=%lld and b_plane_stride=%lld must be at least H * W = %lld", fn, (long long)a_plane_stride,
+                   (long long)b_plane_stride, (long long)plane);
+    const int ny = H / L, nx = W / L;
+    const int64_t wins = (int64_t)ny * nx + (int64_t)ny * (nx - 1) + (int64_t)(ny - 1) * nx + (int64_t)(ny - 1) * (nx - 1);
+    DGMR_CHECK_ARG(N * wins <= (1 << 30), "%s: %lld windows are out of range", fn, (long long)(N * wins));
+    const int wide = (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && a_plane_stride % 4 == 0 && b_plane_stride % 4 == 0;
+    const LagGeom g{a, b, sums, a_plane_stride, b_plane_stride, H, W, (int)wins, wide};
+    hipStream_t st = ST;
+    const int rc = L == 32 ? lag_run<32>(g, N * wins, st) : L == 64 ? lag_run<64>(g, N * wins, st) : lag_run<128>(g, N * wins, st);
+    if (rc != 0) return rc;
     DGMR_CHECK_LAUNCH();
     return 0;
 }

@@ -22,18 +22,29 @@
 Matching and mask act in Lagrangian coordinates: the bilinear advection afterwards blurs the wet / dry edge over a pixel, as it does
 for the deterministic baseline, so a moved member's distribution is the observed one only up to that interpolation.
 
-Limits: no velocity perturbations, and the lifetime law is a fixed power law, not estimated from data; the mask's dilation law is
-fixed as well (radius + growth t), it does not follow the members.  The white field and the result each take M T H W floats: about
+`lifetime_rho` is a fixed power law.  `estimate_rho` measures rho[r] instead, as STEPS does, in Lagrangian coordinates: the context
+frames are advected into the last frame's coordinates (`lagrangian_frames`), `lag_spectra` (`dgmr_lag_spectra`, csrc/spectrum.hip;
+`lag_spectra_reference` is its float64 specification) forms per window and radial bin the sums of |A|^2, |B|^2 and Re(A conj B) of
+consecutive frames over exactly the windows and bins the recursion evolves, and the pooled coherence C / sqrt(Pa Pb) of the windows
+that stay clear of the advection's zero inflow is rho[r].  `EnsembleAdvectionNowcaster(rho="estimate")` does this per call and plane.
+
+Limits: no velocity perturbations; the estimate is lag 1 only (an AR(1) per bin - `lag_spectra` of frames two apart would give an
+AR(2)'s second coefficient, the recursion has no use for it), bilinear advection and motion error bias its high wavenumbers low, and
+a frame too small to keep a window clear of the margin falls back to the law; the mask's dilation law is
+fixed (radius + growth t), it does not follow the members.  The white field and the result each take M T H W floats: about
 1.1 GB each for 8 members and 18 lead times of a 1536 x 1280 frame.
 """
 from __future__ import annotations
 
+import functools
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
 import torch
 
-from .advection import CONTEXT_FRAMES, MAX_STEPS, AdvectionNowcaster, _planes, _stream, advect_series, lattice_geometry, motion_field
+from .advection import (CONTEXT_FRAMES, MAX_STEPS, AdvectionNowcaster, _planes, _stream, advect, advect_series, lattice_geometry,
+                        motion_field)
 from .spectra import _radial_bins
 
 WINDOWS = (32, 64, 128)
@@ -215,6 +226,149 @@ def spectral_ar(z0: torch.Tensor, white: torch.Tensor, rho: torch.Tensor, window
     return out
 
 
+# ---- rho(r) from the context frames ------------------------------------------------------------------------------------------------------
+RhoEstimate = namedtuple("RhoEstimate", ["rho", "windows"])
+
+
+def window_table(h: int, w: int, window: int) -> np.ndarray:
+    """int64 [Wn, 4] = (cy, cx, y0, x0): the windows of `spectral_ar` on an H x W plane in `dgmr_lag_spectra`'s order - class by class
+    in the order (0,0), (0,1), (1,0), (1,1), row-major inside a class; Wn = the sum over the classes of (H / L - cy) (W / L - cx)."""
+    window = _check_window(window)
+    _check_plane(h, w, window)
+    half = window // 2
+    rows = [(cy, cx, i * window + cy * half, j * window + cx * half) for cy in (0, 1) for cx in (0, 1)
+            for i in range(h // window - cy) for j in range(w // window - cx)]
+    return np.array(rows, dtype=np.int64).reshape(-1, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def _bin_matrix(window: int) -> np.ndarray:
+    """float64 [L * L, L]: row k is the indicator of the radial bin of mode k (fft2's order, flattened)"""
+    m = np.zeros((window * window, window))
+    m[np.arange(window * window), _radial_bins(window).reshape(-1)] = 1.0
+    m.setflags(write=False)
+    return m
+
+
+def lag_spectra_reference(a, b, window: int) -> np.ndarray:
+    """The specification of `dgmr_lag_spectra`, in float64 numpy -> float64 [N, Wn, 3, L].
+
+    a, b: fp32 [N, H, W], any finite real values; H and W multiples of L = window, one of 32, 64, 128.  Per plane and window of
+    `window_table(H, W, L)`, with A = fft2(a patch) and B = fft2(b patch), unnormalised, summed over ALL L^2 modes of radial bin r
+    (`spectral_ar_reference`'s r(k), r < L; the corners and the Nyquist row and column are kept):
+      [..., 0, r] = sum |A|^2,   [..., 1, r] = sum |B|^2,   [..., 2, r] = sum Re(A conj B);   0 for a bin without modes."""
+    window = _check_window(window)
+    a = np.asarray(a, dtype=np.float32).astype(np.float64)
+    b = np.asarray(b, dtype=np.float32).astype(np.float64)
+    if a.ndim != 3 or a.shape != b.shape or a.shape[0] < 1:
+        raise ValueError(f"a and b must be [N >= 1, H, W] of one shape, got {a.shape} and {b.shape}")
+    n, h, w = a.shape
+    _check_plane(h, w, window)
+    bins = _bin_matrix(window)
+    blocks = []
+    for cy in (0, 1):
+        for cx in (0, 1):
+            ny, nx = h // window - cy, w // window - cx
+            if ny == 0 or nx == 0:
+                continue
+            fa = np.fft.fft2(_class_windows(a, window, cy, cx)).reshape(n, ny * nx, window * window)
+            fb = np.fft.fft2(_class_windows(b, window, cy, cx)).reshape(n, ny * nx, window * window)
+            terms = np.stack([fa.real ** 2 + fa.imag ** 2, fb.real ** 2 + fb.imag ** 2, fa.real * fb.real + fa.imag * fb.imag], axis=2)
+            blocks.append(terms @ bins)  # [N, ny nx, 3, L]
+    return np.concatenate(blocks, axis=1)
+
+
+def lag_spectra(a: torch.Tensor, b: torch.Tensor, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`lag_spectra_reference` for torch tensors -> float64 [N, Wn, 3, L] on the inputs' device.
+
+    a, b: fp32 [N, H, W] (contiguous planes, any plane stride each; anything else is copied).  out: a contiguous float64
+    [N, Wn, 3, L] tensor or view.  On a HIP device one `dgmr_lag_spectra` on the current stream, nothing synchronised, no workspace;
+    16-byte loads where both pointers and strides allow them.  On the CPU the float64 reference."""
+    window = _check_window(window)
+    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise ValueError(f"a {tuple(a.shape)} on {a.device} and b {tuple(b.shape)} on {b.device} must match")
+    a, sa = _planes(a, "a")
+    b, sb = _planes(b, "b")
+    n, h, w = (int(v) for v in a.shape)
+    if n < 1:
+        raise ValueError("a and b hold no plane")
+    wn = window_table(h, w, window).shape[0]
+    if out is None:
+        out = torch.empty((n, wn, 3, window), dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (n, wn, 3, window) or out.dtype != torch.float64 or out.device != a.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{n}, {wn}, 3, {window}] tensor on {a.device}")
+    if not a.is_cuda:
+        out.copy_(torch.from_numpy(lag_spectra_reference(a.numpy(), b.numpy(), window)))
+        return out
+    from ._lib import call
+
+    device = a.device
+    with torch.cuda.device(device):
+        call("dgmr_lag_spectra", a.data_ptr(), sa, b.data_ptr(), sb, n, h, w, window, out.data_ptr(), _stream(device))
+    return out
+
+
+def lagrangian_frames(z: torch.Tensor, field: torch.Tensor, origin: float = 0.0, spacing: float = 1.0) -> torch.Tensor:
+    """The context in the last frame's coordinates -> fp32 [K, P, H, W]: frame k of z (fp32 [K, P, H, W], time order) moved K - 1 - k
+    steps along `field` ([P or 1, Gy, Gx, 2], pixels per step) - the last lead time of one `advect` call per frame -, the newest
+    frame as it is.  `advect`'s rules hold: bilinear interpolation, a tap outside the frame is 0 (so a band of up to
+    (K - 1) max|field| pixels along the inflow border is not the field moved but zeros), values below 0 read as 0 (dB fields of
+    `to_db` have none)."""
+    if z.dim() != 4 or z.dtype != torch.float32 or z.shape[0] < 1:
+        raise ValueError(f"z must be a float32 [K >= 1, P, H, W] tensor, got {z.dtype} {tuple(z.shape)}")
+    k = int(z.shape[0])
+    out = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+    out[k - 1].copy_(z[k - 1])
+    for i in range(k - 1):
+        out[i].copy_(advect(z[i], field, k - 1 - i, origin, spacing)[:, -1])
+    return out
+
+
+def estimate_rho(z: torch.Tensor, field: torch.Tensor, origin: float, spacing: float, window: int, margin: Optional[int] = None,
+                 fallback: Optional[torch.Tensor] = None) -> RhoEstimate:
+    """The lag-1 correlation per radial bin from K context frames -> RhoEstimate(rho fp32 [P, L], windows float64 [P]).
+
+    z: fp32 [K >= 2, P, H, W] in time order (dB fields); field, origin, spacing: the motion of `motion_field` / `lattice_geometry`.
+    The frames are brought to the last frame's coordinates (`lagrangian_frames`), one `lag_spectra` call forms the sums of the K - 1
+    consecutive pairs, and they are pooled in float64 over the pairs and over the windows that are used: a window is used iff
+    min(y0, x0, H - y0 - L, W - x0 - L) >= margin - the zero inflow of the advection contaminates every window it reaches.  margin:
+    None for ceil((K - 1) max|field|) + 1 per plane, computed and applied on the device (a 0 / 1 weight per window: nothing is
+    synchronised); 0 uses every window.  With the pooled Pa = sum |A|^2, Pb = sum |B|^2, C = sum Re(A conj B) of a bin:
+      rho[r] = clip(C / sqrt(Pa Pb), 0, 1);  rho[0] = 1 (a window keeps its mean, as in `lifetime_rho`);
+      rho[r] = fallback[r] where Pa Pb == 0 - a bin without modes, a dry pool, a pool with no window left.
+    fallback: fp32 [L], default `lifetime_rho(window)`.  windows: how many windows each plane's pool used.
+    Lag 1 only; the bilinear advection and motion error bias high wavenumbers low."""
+    window = _check_window(window)
+    if z.dim() != 4 or z.dtype != torch.float32 or z.shape[0] < 2:
+        raise ValueError(f"z must be a float32 [K >= 2, P, H, W] tensor, got {z.dtype} {tuple(z.shape)}")
+    k, p, h, w = (int(v) for v in z.shape)
+    _check_plane(h, w, window)
+    device = z.device
+    fallback = lifetime_rho(window) if fallback is None else torch.as_tensor(fallback, dtype=torch.float32)
+    if tuple(fallback.shape) != (window,):
+        raise ValueError(f"fallback must hold {window} values, got shape {tuple(fallback.shape)}")
+    frames = lagrangian_frames(z, field, origin, spacing)
+    sums = lag_spectra(frames[:-1].reshape((k - 1) * p, h, w), frames[1:].reshape((k - 1) * p, h, w), window)
+    table = window_table(h, w, window)
+    edge = np.minimum(np.minimum(table[:, 2], table[:, 3]), np.minimum(h - table[:, 2] - window, w - table[:, 3] - window))
+    edge = torch.from_numpy(edge.astype(np.float64)).to(device)
+    if margin is None:
+        speed = field.abs().reshape(field.shape[0], -1).amax(dim=1).to(torch.float64)  # [P or 1]
+        need = torch.ceil((k - 1) * speed) + 1.0
+    else:
+        if int(margin) < 0:
+            raise ValueError(f"margin={margin} must not be negative")
+        need = torch.full((1,), float(int(margin)), dtype=torch.float64, device=device)
+    weight = (edge[None, :] >= need.expand(p)[:, None]).to(torch.float64)  # [P, Wn]
+    pooled = (sums.view(k - 1, p, -1, 3, window) * weight[None, :, :, None, None]).sum(dim=(0, 2))  # [P, 3, L]
+    den = pooled[:, 0] * pooled[:, 1]
+    ok = den > 0
+    gamma = pooled[:, 2] / torch.sqrt(torch.where(ok, den, torch.ones_like(den)))
+    rho = torch.where(ok, gamma.clamp(0.0, 1.0).to(torch.float32), fallback.to(device)[None, :].expand(p, window)).contiguous()
+    rho[:, 0] = 1.0
+    return RhoEstimate(rho, weight.sum(dim=1))
+
+
 # ---- probability matching and the precipitation mask -----------------------------------------------------------------------------------
 def _check_bins(lo: float, scale: float):
     lo, scale = float(lo), float(scale)
@@ -357,7 +511,10 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     """`AdvectionNowcaster` with `num_members` stochastic members: the last frame in dB evolves per window and Fourier mode by
     `spectral_ar` in Lagrangian coordinates, every member is then moved along the context's motion field (`advect_series`, the
     members of a case sharing its field) and taken back to rain rates.  window: L of `spectral_ar` (H and W must be multiples);
-    threshold, pad: `to_db`'s; rho: fp32 [window] lag-1 correlations per radial wavenumber, None for `lifetime_rho(window)`.
+    threshold, pad: `to_db`'s; rho: fp32 [window] lag-1 correlations per radial wavenumber, None for `lifetime_rho(window)`, or
+    "estimate": every call estimates them per plane from the dB transform of the context frames that give the motion (`estimate_rho`
+    with its default margin, `lifetime_rho(window)` as the fallback), keeps them as `last_rho` (fp32 [planes, window]; `last_windows`:
+    the windows each pool used) and runs one `spectral_ar` per plane.
     probability_matching: match every member and lead time to the last observed dB frame (`probability_match`, in place, before the
     advection); mask_radius (needs the matching): None for no mask, else `precipitation_mask`'s radius in pixels, mask_growth its
     growth in pixels per lead time.  The defaults leave all three off."""
@@ -376,10 +533,14 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         self.mask_growth = float(mask_growth)
         self.window = _check_window(window)
         self.threshold, self.pad = float(threshold), float(pad)
-        rho = lifetime_rho(self.window) if rho is None else torch.as_tensor(rho, dtype=torch.float32)
+        self.estimate = isinstance(rho, str)
+        if self.estimate and rho != "estimate":
+            raise ValueError(f"rho={rho!r}: a tensor, None or \"estimate\" is required")
+        rho = lifetime_rho(self.window) if rho is None or self.estimate else torch.as_tensor(rho, dtype=torch.float32)
         if tuple(rho.shape) != (self.window,):
             raise ValueError(f"rho must hold {self.window} values, got shape {tuple(rho.shape)}")
-        self.rho = rho
+        self.rho = rho  # with rho="estimate": the fallback of `estimate_rho`
+        self.last_rho = self.last_windows = None
 
     def white_noise(self, planes: int, num_members: int, h: int, w: int, device, seed: int = 0) -> torch.Tensor:
         """The unit Gaussian field `nowcast` draws for `seed`: fp32 [planes, M, T, H, W] from a seeded `torch.Generator` on `device`."""
@@ -402,7 +563,15 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         self.last_field = motion_field(context[-CONTEXT_FRAMES:], **self.params)
         origin, spacing = lattice_geometry(self.params["block"], self.params["stride"])
         z0 = to_db(context[-1], self.threshold, self.pad)
-        z = spectral_ar(z0, white, self.rho.to(context.device), self.window)
+        if self.estimate:
+            est = estimate_rho(to_db(context[-CONTEXT_FRAMES:], self.threshold, self.pad), self.last_field, origin, spacing, self.window,
+                               fallback=self.rho)
+            self.last_rho, self.last_windows = est
+            z = torch.empty(shape, dtype=torch.float32, device=context.device)
+            for i in range(planes):  # a rho of its own per plane: one launch each, into views
+                spectral_ar(z0[i:i + 1], white[i:i + 1], self.last_rho[i], self.window, out=z[i:i + 1])
+        else:
+            z = spectral_ar(z0, white, self.rho.to(context.device), self.window)
         if self.probability_matching:
             mask = None
             if self.mask_radius is not None:
