@@ -762,6 +762,28 @@ int dgmr_lag_spectra(const float* a, int64_t a_plane_stride, const float* b, int
                      double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * dgmr_spectral_ar2: dgmr_spectral_ar with a second lag (stochastic.py: spectral_ar2, ar2_coefficients, estimate_ar2;
+ * csrc/spectrum.hip).  New symbol, same ABI version.
+ * z0, white, out, P, M, T, H, W, L, the windows, their classes, the radial bin r(k), the blend and the four launches are
+ * dgmr_spectral_ar's.  zm1: the frame before z0 in z0's coordinates, P fp32 planes [H][W], zm1_plane_stride apart.  coef: per plane
+ * three rows of L fp32 values (phi1[r], phi2[r], g[r]), plane p at coef + p coef_plane_stride; coef_plane_stride = 0 is one set for
+ * all planes, otherwise it is at least 3 L.  Per window and member, with X_0 = fft2(z0 patch), X_-1 = fft2(zm1 patch),
+ * A = |X_0| / L and Wh_t = fft2(white patch of lead t):
+ *   X_t(k) = (phi1[r(k)] X_(t-1)(k) + phi2[r(k)] X_(t-2)(k)) + g[r(k)] A(k) Wh_t(k),   x_t = real(ifft2(X_t)),   t = 1 ... T.
+ * The coefficients are used as passed, never recomputed: per component X_t = fma(phi1, X_(t-1), fma(phi2, X_(t-2), amp v)) with
+ * amp = g[r] (|X_0| (1 / L)), so coef = (rho, 0, fp32(sqrt(1 - rho^2))) is dgmr_spectral_ar's recursion term for term.  Both spectra
+ * of a thread's elements stay in registers through the T steps; phi1 and phi2 are read from LDS tables by the element's radial bin,
+ * kept as packed bytes; zm1 is transformed once, before the loop, in the one LDS buffer.  No atomics, no workspace, two calls give
+ * the same bits.  16-byte accesses when pointers and strides allow them (z0, zm1 and white together, out on its own).  Argument
+ * errors (null pointers, L outside the set, H or W not a multiple of L, T outside 1 ... 64, P or M below 1, a negative stride, a
+ * white or out stride below H * W, a coef stride between 1 and 3 L - 1) return < 0 and set dgmr_last_error() before anything is
+ * enqueued.  Runs on `stream`, does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_spectral_ar2(const float* z0, int64_t z0_plane_stride, const float* zm1, int64_t zm1_plane_stride, const float* white,
+                      int64_t white_member_stride, int64_t white_step_stride, const float* coef, int64_t coef_plane_stride, int P, int M,
+                      int T, int H, int W, int L, float* out, int64_t out_member_stride, int64_t out_step_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Probability matching for the stochastic ensemble (stochastic.py: probability_match; csrc/probmatch.hip).  New symbols, same ABI
  * version.
  * z: the dB fields of dgmr_spectral_ar with its plane addressing - plane n = p M + m of lead time t at z + n member_stride +

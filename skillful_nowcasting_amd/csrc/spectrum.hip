@@ -1,8 +1,9 @@
 // The two remaining verification plots on the device (spectra.py, value.py): the radially averaged power spectral density of L x L
 // windows (dgmr_radial_psd) and the exceedance table that reliability, Brier score, ROC points and economic value are derived from
 // (dgmr_exceedance_table).  And, built on the PSD's transforms, the AR(1) noise windows of the stochastic advection ensemble
-// (stochastic.py: dgmr_spectral_ar; its section below says how) and, on the same windows and bins, the radially binned cross-spectrum
-// of two planes that the estimate of the recursion's rho(r) pools (dgmr_lag_spectra; its section too).
+// (stochastic.py: dgmr_spectral_ar; its section below says how), the same with a second lag (dgmr_spectral_ar2) and, on the same
+// windows and bins, the radially binned cross-spectrum of two planes that the estimate of the recursion's rho(r) pools
+// (dgmr_lag_spectra; its section too).
 //
 // PSD.  fp32 radix-2 decimation-in-frequency transforms in LDS (two stages per pass and barrier), twiddles from a table of exp(-2 pi i k / 512) computed in double and
 // rounded to fp32 (psd_twiddle_kernel writes it to the head of the workspace; every kernel copies it to LDS).  The input is real, so
@@ -624,6 +625,183 @@ int ar_allow_lds() {
     return 0;
 }
 
+// ---- spectral AR(2) noise windows (stochastic.py: spectral_ar2) --------------------------------------------------------------------------
+// spectral_ar_kernel with a second lag: X_t = phi1 X_(t-1) + phi2 X_(t-2) + g A Wh_t per mode, the coefficients per radial bin as
+// passed (coef: [3][L] per plane, or one set for all).  Same workgroups, LDS buffer, transforms, blend and launches.  A thread holds
+// BOTH spectra of its elements and the noise amplitude through the T steps: 5 registers per element, 85 at L = 128 (17 elements).
+// phi1 and phi2 per element would make that 119, past the 128 that two workgroups of 512 threads on a CU may take, so they stay in
+// two LDS tables of L floats and a thread keeps only the radial bin of each element, a byte (r < L <= 128), four to a register.
+// zm1 is transformed first, in the same buffer, and kept as X_(t-2); then z0 as X_(t-1), which also gives the amplitude.
+// Left to itself the compiler undoes the packing: it hoists the T-loop's invariants - the 17 extracted bins, the transforms'
+// addresses - into registers of their own (184 VGPRs at L = 128: one workgroup per CU, 8.1 ms against spectral_ar's 5.0 ms on the
+// 1536 x 1280, M = 8, T = 18 nowcast), and capped at 128 it spills them to scratch.  So every step starts from an opaque copy of
+// the thread index and of the packed bins (two empty asm statements: no instruction, only a value the optimiser cannot follow across
+// the iteration) and re-derives both, a few integer operations per element and step.  Allocation (code object metadata, no scratch
+// at any L): 60 VGPRs at L = 32, 81 at L = 64, 122 at L = 128 - two workgroups per CU (4 waves per SIMD), as spectral_ar_kernel.
+struct Ar2Geom {
+    const float* z0;
+    const float* zm1;
+    const float* white;
+    const float* coef;
+    float* out;
+    int64_t z0_plane_stride, zm1_plane_stride, coef_plane_stride, white_member_stride, white_step_stride, out_member_stride, out_step_stride;
+    int M, T, H, W, cy, cx, wins_y, wins_x;  // wins: the windows of this class per plane
+    int wide_in, wide_out;                   // 16-byte accesses allowed for z0, zm1 and white / for out
+};
+
+template <int L>
+constexpr int ar2_lds() { return ar_lds<L>() + L * 4; }  // five rows of L floats: phi1, phi2, g and the two blend weight rows
+
+template <int L>
+__global__ __launch_bounds__(psd_threads(L), L == 128 ? 4 : 1) void spectral_ar2_kernel(Ar2Geom g) {  // (512 threads, 4 waves per SIMD)
+    constexpr int NT = psd_threads(L), NH = L / 2, RS = NH + 1, TOTAL = L * RS, NS = ar_state(L), NB = (NS + 3) / 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char psd_smem[];
+    float2* s = (float2*)psd_smem;           // [L][RS]
+    float2* tw = s + TOTAL;                  // [PSD_TW]
+    float* s_phi1 = (float*)(tw + PSD_TW);   // [L]
+    float* s_phi2 = s_phi1 + L;              // [L]
+    float* s_g = s_phi2 + L;                 // [L]
+    float* s_wy = s_g + L;                   // [L]: this window's blend weights down the rows ...
+    float* s_wx = s_wy + L;                  // [L]: ... and along them
+    const int tid = threadIdx.x;
+    const int per_plane = g.wins_y * g.wins_x;
+    const int64_t n = blockIdx.x / per_plane;  // plane * M + member
+    const int wi = (int)(blockIdx.x - n * per_plane);
+    const int wy = wi / g.wins_x, wx = wi - wy * g.wins_x;
+    const int y0 = wy * L + g.cy * NH, x0 = wx * L + g.cx * NH;  // y0 + L <= H, x0 + L <= W
+    const int64_t p = n / g.M;
+    for (int i = tid; i < PSD_TW; i += NT) {
+        double sn, cs;
+        sincospi(-(double)i / 256.0, &sn, &cs);
+        tw[i] = make_float2((float)cs, (float)sn);
+    }
+    const float* coef = g.coef + p * g.coef_plane_stride;  // [3][L]
+    for (int i = tid; i < L; i += NT) {
+        s_phi1[i] = coef[i];
+        s_phi2[i] = coef[L + i];
+        s_g[i] = coef[2 * L + i];
+        // the blend weights of spectral_ar_kernel
+        const double sh = sinpi(((double)i + 0.5) / (double)L), sc = sinpi(((double)((i + NH) % L) + 0.5) / (double)L);
+        const float h_own = (float)(sh * sh), h_other = (float)(sc * sc);
+        const int Y = y0 + i, X = x0 + i;
+        s_wy[i] = g.cy ? h_own : (Y < NH || Y >= g.H - NH) ? 1.f : 1.f - h_other;
+        s_wx[i] = g.cx ? h_own : (X < NH || X >= g.W - NH) ? 1.f : 1.f - h_other;
+    }
+    __syncthreads();
+    const int64_t origin = (int64_t)y0 * g.W + x0;
+    float2 X1[NS], X2[NS];  // X_(t-1), X_(t-2)
+    float amp[NS];
+    unsigned int bins[NB];  // the radial bin of element j: byte j % 4 of bins[j / 4] (formed first: nothing else is live yet)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) bins[b] = 0u;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        if (e < TOTAL) {
+            const int row = e / RS, c = e - row * RS;
+            int ky = brev<ilog2(L)>(row);
+            ky = ky >= NH ? ky - L : ky;
+            const int kx = c < NH ? brev<ilog2(NH)>(c) : NH;
+            const int d2 = kx * kx + ky * ky;
+            const int k = isqrt_floor(d2);
+            const int r = d2 <= k * (k + 1) ? k : k + 1;  // r (r - 1) < d2 <= r (r + 1); r <= L / sqrt(2) + 1 < L <= 128: a byte
+            bins[j >> 2] |= (unsigned int)r << (8 * (j & 3));
+        }
+    }
+    ar_load<L, NT>(s, g.zm1 + p * g.zm1_plane_stride + origin, g.W, g.wide_in, tid);
+    ar_forward<L>(s, tw, tid);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        X2[j] = e < TOTAL ? s[e] : make_float2(0.f, 0.f);
+    }
+    __syncthreads();  // everyone holds its part of X_-1 before the buffer is loaded again
+    ar_load<L, NT>(s, g.z0 + p * g.z0_plane_stride + origin, g.W, g.wide_in, tid);
+    ar_forward<L>(s, tw, tid);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int e = tid + j * NT;
+        X1[j] = make_float2(0.f, 0.f);
+        amp[j] = 0.f;
+        if (e < TOTAL) {
+            const int r = (int)((bins[j >> 2] >> (8 * (j & 3))) & 255u);
+            X1[j] = s[e];
+            amp[j] = s_g[r] * (sqrtf(X1[j].x * X1[j].x + X1[j].y * X1[j].y) * (1.f / (float)L));
+        }
+    }
+    const float* wh = g.white + n * g.white_member_stride + origin;
+    float* out = g.out + n * g.out_member_stride + origin;
+    constexpr float INV = 1.f / ((float)L * (float)L);
+    for (int t = 0; t < g.T; ++t) {
+        int lt = tid;  // this step's thread index and bins: the same values, opaque (see the section's comment)
+        asm volatile("" : "+v"(lt));
+#pragma unroll
+        for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(bins[b]));
+        __syncthreads();  // the reads of the step before (or of the state) are done
+        ar_load<L, NT>(s, wh + (int64_t)t * g.white_step_stride, g.W, g.wide_in, lt);
+        ar_forward<L>(s, tw, lt);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int e = lt + j * NT;
+            if (e < TOTAL) {
+                const float2 v = s[e];
+                const int r = (int)((bins[j >> 2] >> (8 * (j & 3))) & 255u);
+                const float p1 = s_phi1[r], p2 = s_phi2[r];
+                const float2 nx = make_float2(fmaf(p1, X1[j].x, fmaf(p2, X2[j].x, amp[j] * v.x)),
+                                              fmaf(p1, X1[j].y, fmaf(p2, X2[j].y, amp[j] * v.y)));
+                X2[j] = X1[j];
+                X1[j] = nx;
+                s[e] = nx;
+            }
+        }
+        __syncthreads();
+        fft_dit_inverse<L, NH + 1, RS, 1, NT>(s, tw, lt);
+        real_merge<L, L, RS, NT>(s, tw, lt);
+        fft_dit_inverse<NH, L, 1, RS, NT>(s, tw, lt);
+        float* o = out + (int64_t)t * g.out_step_stride;
+        const bool first = g.cy == 0 && g.cx == 0;
+        for (int i = lt; i < L * (L / 4); i += NT) {
+            const int q = i % (L / 4), y = i / (L / 4);
+            const float2 a = s[y * RS + 2 * q], b = s[y * RS + 2 * q + 1];
+            const float wrow = s_wy[y];
+            const float w0 = wrow * s_wx[4 * q], w1 = wrow * s_wx[4 * q + 1], w2 = wrow * s_wx[4 * q + 2], w3 = wrow * s_wx[4 * q + 3];
+            float* d = o + (int64_t)y * g.W + 4 * q;
+            f32x4 v;
+            if (first) {
+                v.x = (a.x * INV) * w0, v.y = (a.y * INV) * w1, v.z = (b.x * INV) * w2, v.w = (b.y * INV) * w3;
+            } else {
+                if (g.wide_out) {
+                    v = *(const f32x4*)d;
+                } else {
+                    v.x = d[0], v.y = d[1], v.z = d[2], v.w = d[3];
+                }
+                v.x = fmaf(a.x * INV, w0, v.x), v.y = fmaf(a.y * INV, w1, v.y), v.z = fmaf(b.x * INV, w2, v.z), v.w = fmaf(b.y * INV, w3, v.w);
+            }
+            if (g.wide_out) {
+                *(f32x4*)d = v;
+            } else {
+                d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+            }
+        }
+    }
+}
+
+template <int L>
+int ar2_run(const Ar2Geom& g, int64_t blocks, hipStream_t st) {
+    hipLaunchKernelGGL(spectral_ar2_kernel<L>, dim3((unsigned)blocks), dim3(psd_threads(L)), ar2_lds<L>(), st, g);
+    return 0;
+}
+
+template <int L>
+int ar2_allow_lds() {
+    if (ar2_lds<L>() <= 64 * 1024) return 0;
+    if (hipFuncSetAttribute((const void*)spectral_ar2_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, ar2_lds<L>()) != hipSuccess) {
+        dgmr_set_error("dgmr_spectral_ar2: %d bytes of LDS per workgroup were refused: %s", ar2_lds<L>(), hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    return 0;
+}
+
 // ---- lag spectra (stochastic.py: lag_spectra, estimate_rho) ----------------------------------------------------------------------------
 // One workgroup per (plane, window), the four window classes of the recursion in one launch.  The `b` patch is transformed first and
 // its half spectrum kept in registers (ar_state(L) elements per thread, as spectral_ar_kernel holds X), the `a` patch is transformed
@@ -915,6 +1093,58 @@ extern "C" int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const 
             ar_run<64>(g, blocks, st);
         else
             ar_run<128>(g, blocks, st);
+    }
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_spectral_ar2(const float* z0, int64_t z0_plane_stride, const float* zm1, int64_t zm1_plane_stride, const float* white,
+                                 int64_t white_member_stride, int64_t white_step_stride, const float* coef, int64_t coef_plane_stride, int P,
+                                 int M, int T, int H, int W, int L, float* out, int64_t out_member_stride, int64_t out_step_stride,
+                                 void* stream) {
+    const char* fn = "dgmr_spectral_ar2";
+    DGMR_CHECK_ARG(L == 32 || L == 64 || L == 128, "%s: window L=%d is not one of 32, 64, 128", fn, L);
+    DGMR_CHECK_ARG(T >= 1 && T <= 64, "%s: T=%d lead times, 1 ... 64 are supported", fn, T);
+    DGMR_CHECK_ARG(P >= 1 && M >= 1 && (int64_t)P * M <= (1 << 24), "%s: P=%d planes of M=%d members are out of range", fn, P, M);
+    DGMR_CHECK_ARG(H > 0 && W > 0 && H % L == 0 && W % L == 0, "%s: H=%d and W=%d must be positive multiples of the window L=%d", fn, H, W, L);
+    DGMR_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(z0 && zm1 && white && coef && out, "%s: null pointer", fn);
+    const int64_t N = (int64_t)P * M, plane = (int64_t)H * W, cap = INT64_MAX / 4 / (N * 64);
+    DGMR_CHECK_ARG(z0_plane_stride >= 0 && z0_plane_stride <= cap && zm1_plane_stride >= 0 && zm1_plane_stride <= cap,
+                   "%s: z0_plane_stride=%lld or zm1_plane_stride=%lld out of range", fn, (long long)z0_plane_stride,
+                   (long long)zm1_plane_stride);
+    DGMR_CHECK_ARG(coef_plane_stride == 0 || (coef_plane_stride >= 3 * L && coef_plane_stride <= cap),
+                   "%s: coef_plane_stride=%lld must be 0 (one set for all planes) or at least 3 L = %d", fn, (long long)coef_plane_stride, 3 * L);
+    DGMR_CHECK_ARG((N == 1 || (white_member_stride >= plane && white_member_stride <= cap)) &&
+                       (T == 1 || (white_step_stride >= plane && white_step_stride <= cap)),
+                   "%s: white_member_stride=%lld and white_step_stride=%lld must be at least H * W = %lld", fn,
+                   (long long)white_member_stride, (long long)white_step_stride, (long long)plane);
+    DGMR_CHECK_ARG((N == 1 || (out_member_stride >= plane && out_member_stride <= cap)) &&
+                       (T == 1 || (out_step_stride >= plane && out_step_stride <= cap)),
+                   "%s: out_member_stride=%lld and out_step_stride=%lld must be at least H * W = %lld", fn, (long long)out_member_stride,
+                   (long long)out_step_stride, (long long)plane);
+    DGMR_CHECK_ARG(N * (H / L) * (W / L) <= (1 << 30), "%s: %lld windows are out of range", fn, (long long)(N * (H / L) * (W / L)));
+    const int64_t wms = N == 1 ? 0 : white_member_stride, wss = T == 1 ? 0 : white_step_stride;
+    const int64_t oms = N == 1 ? 0 : out_member_stride, oss = T == 1 ? 0 : out_step_stride;
+    const int wide_in = (((uintptr_t)z0 | (uintptr_t)zm1 | (uintptr_t)white) & 15) == 0 && z0_plane_stride % 4 == 0 &&
+                        zm1_plane_stride % 4 == 0 && wms % 4 == 0 && wss % 4 == 0;
+    const int wide_out = ((uintptr_t)out & 15) == 0 && oms % 4 == 0 && oss % 4 == 0;
+    const int rc = L == 32 ? ar2_allow_lds<32>() : L == 64 ? ar2_allow_lds<64>() : ar2_allow_lds<128>();
+    if (rc != 0) return rc;
+    hipStream_t st = ST;
+    for (int c = 0; c < 4; ++c) {  // (0,0) stores; (0,1), (1,0), (1,1) add, in this order
+        const int cy = c >> 1, cx = c & 1;
+        const int wins_y = H / L - cy, wins_x = W / L - cx;
+        if (wins_y == 0 || wins_x == 0) continue;
+        const Ar2Geom g{z0, zm1, white, coef, out, z0_plane_stride, zm1_plane_stride, coef_plane_stride, wms, wss, oms, oss, M, T, H, W,
+                        cy, cx, wins_y, wins_x, wide_in, wide_out};
+        const int64_t blocks = N * wins_y * wins_x;
+        if (L == 32)
+            ar2_run<32>(g, blocks, st);
+        else if (L == 64)
+            ar2_run<64>(g, blocks, st);
+        else
+            ar2_run<128>(g, blocks, st);
     }
     DGMR_CHECK_LAUNCH();
     return 0;

@@ -28,9 +28,15 @@ frames are advected into the last frame's coordinates (`lagrangian_frames`), `la
 consecutive frames over exactly the windows and bins the recursion evolves, and the pooled coherence C / sqrt(Pa Pb) of the windows
 that stay clear of the advection's zero inflow is rho[r].  `EnsembleAdvectionNowcaster(rho="estimate")` does this per call and plane.
 
-Limits: no velocity perturbations; the estimate is lag 1 only (an AR(1) per bin - `lag_spectra` of frames two apart would give an
-AR(2)'s second coefficient, the recursion has no use for it), bilinear advection and motion error bias its high wavenumbers low, and
-a frame too small to keep a window clear of the margin falls back to the law; the mask's dilation law is
+`spectral_ar2` (`dgmr_spectral_ar2`; `spectral_ar2_reference`) is the same recursion with a second lag, X_t = phi1 X_(t-1) +
+phi2 X_(t-2) + g A Wh_t, started from the last two frames; `estimate_ar2` adds the pooled coherence of frames two apart and
+`ar2_coefficients` solves Yule-Walker per bin (clipped so that the process stays bounded, keeps rho1 and has unit variance);
+`EnsembleAdvectionNowcaster(order=2)` uses them.
+
+Limits: no velocity perturbations; the AR(2) is per radial bin and from coherences, not per cascade level from pixel correlations
+as in STEPS, its Yule-Walker solution is ill-conditioned near rho1 = 1, its second state carries the advection's zero inflow at
+the border and its noise amplitude comes from the last frame alone; bilinear advection and motion error bias the estimate's high
+wavenumbers low, and a frame too small to keep a window clear of the margin falls back to the law; the mask's dilation law is
 fixed (radius + growth t), it does not follow the members.  The white field and the result each take M T H W floats: about
 1.1 GB each for 8 members and 18 lead times of a 1536 x 1280 frame.
 """
@@ -338,6 +344,13 @@ def estimate_rho(z: torch.Tensor, field: torch.Tensor, origin: float, spacing: f
       rho[r] = fallback[r] where Pa Pb == 0 - a bin without modes, a dry pool, a pool with no window left.
     fallback: fp32 [L], default `lifetime_rho(window)`.  windows: how many windows each plane's pool used.
     Lag 1 only; the bilinear advection and motion error bias high wavenumbers low."""
+    frames, weight, fallback = _lagrangian_pool(z, field, origin, spacing, window, margin, fallback)
+    return RhoEstimate(_lag1_rho(frames, weight, fallback, window), weight.sum(dim=1))
+
+
+def _lagrangian_pool(z, field, origin, spacing, window, margin, fallback):
+    """The checks of `estimate_rho` -> (the Lagrangian frames [K, P, H, W], the 0 / 1 weight of every window in the pool float64
+    [P, Wn], the fallback fp32 [L])"""
     window = _check_window(window)
     if z.dim() != 4 or z.dtype != torch.float32 or z.shape[0] < 2:
         raise ValueError(f"z must be a float32 [K >= 2, P, H, W] tensor, got {z.dtype} {tuple(z.shape)}")
@@ -348,7 +361,6 @@ def estimate_rho(z: torch.Tensor, field: torch.Tensor, origin: float, spacing: f
     if tuple(fallback.shape) != (window,):
         raise ValueError(f"fallback must hold {window} values, got shape {tuple(fallback.shape)}")
     frames = lagrangian_frames(z, field, origin, spacing)
-    sums = lag_spectra(frames[:-1].reshape((k - 1) * p, h, w), frames[1:].reshape((k - 1) * p, h, w), window)
     table = window_table(h, w, window)
     edge = np.minimum(np.minimum(table[:, 2], table[:, 3]), np.minimum(h - table[:, 2] - window, w - table[:, 3] - window))
     edge = torch.from_numpy(edge.astype(np.float64)).to(device)
@@ -360,13 +372,189 @@ def estimate_rho(z: torch.Tensor, field: torch.Tensor, origin: float, spacing: f
             raise ValueError(f"margin={margin} must not be negative")
         need = torch.full((1,), float(int(margin)), dtype=torch.float64, device=device)
     weight = (edge[None, :] >= need.expand(p)[:, None]).to(torch.float64)  # [P, Wn]
-    pooled = (sums.view(k - 1, p, -1, 3, window) * weight[None, :, :, None, None]).sum(dim=(0, 2))  # [P, 3, L]
+    return frames, weight, fallback
+
+
+def _pooled_coherence(frames: torch.Tensor, lag: int, weight: torch.Tensor, window: int):
+    """One `lag_spectra` call over the K - lag pairs of frames `lag` apart, pooled in float64 over the pairs and the weighted windows
+    -> (gamma = C / sqrt(Pa Pb) float64 [P, L], ok = Pa Pb > 0 bool [P, L]; gamma is C where not ok)"""
+    k, p, h, w = (int(v) for v in frames.shape)
+    sums = lag_spectra(frames[:-lag].reshape((k - lag) * p, h, w), frames[lag:].reshape((k - lag) * p, h, w), window)
+    pooled = (sums.view(k - lag, p, -1, 3, window) * weight[None, :, :, None, None]).sum(dim=(0, 2))  # [P, 3, L]
     den = pooled[:, 0] * pooled[:, 1]
     ok = den > 0
-    gamma = pooled[:, 2] / torch.sqrt(torch.where(ok, den, torch.ones_like(den)))
-    rho = torch.where(ok, gamma.clamp(0.0, 1.0).to(torch.float32), fallback.to(device)[None, :].expand(p, window)).contiguous()
+    return pooled[:, 2] / torch.sqrt(torch.where(ok, den, torch.ones_like(den))), ok
+
+
+def _lag1_rho(frames: torch.Tensor, weight: torch.Tensor, fallback: torch.Tensor, window: int) -> torch.Tensor:
+    p = int(frames.shape[1])
+    gamma, ok = _pooled_coherence(frames, 1, weight, window)
+    rho = torch.where(ok, gamma.clamp(0.0, 1.0).to(torch.float32), fallback.to(frames.device)[None, :].expand(p, window)).contiguous()
     rho[:, 0] = 1.0
-    return RhoEstimate(rho, weight.sum(dim=1))
+    return rho
+
+
+# ---- the second lag: AR(2) ---------------------------------------------------------------------------------------------------------------
+Ar2Estimate = namedtuple("Ar2Estimate", ["rho1", "rho2", "coef", "windows", "previous"])
+
+
+def ar2_coefficients(rho1: torch.Tensor, rho2: torch.Tensor) -> torch.Tensor:
+    """The AR(2) recursion's coefficients per radial bin from the lag-1 and lag-2 correlations -> fp32 [..., 3, L] = (phi1, phi2, g)
+    on the inputs' device; rho1, rho2: [..., L] of one shape.  Computed in float64, rounded once.  With r1 = clip(rho1, 0, 1) and
+    r2 = clip(rho2, -1, 1):
+      where r1 = 1: (1, 0, 0) - the mode is kept, as bin 0 is by `lifetime_rho`;
+      elsewhere phi2 = clip((r2 - r1^2) / (1 - r1^2), -1, 1), and 0 where rho2 is NaN (no second lag measured);
+                phi1 = r1 (1 - phi2);  g = sqrt((1 - phi2^2) (1 - r1^2)).
+    Yule-Walker wherever the clip is inactive: the process X_t = phi1 X_(t-1) + phi2 X_(t-2) + g e_t with unit white e has lag-1
+    autocorrelation r1 (whatever the clip does: phi1 / (1 - phi2) = r1), lag-2 autocorrelation phi1 r1 + phi2 = r2 and stationary
+    variance 1 (g^2 = (1 - phi2^2)(1 - r1^2) is that variance's innovation).  r1 < 1 and |phi2| <= 1 keep every characteristic root
+    in the closed unit disc, a root on the circle simple: the recursion is bounded.  phi2 = 0 is the AR(1) of r1 with its gain."""
+    if tuple(rho1.shape) != tuple(rho2.shape) or rho1.dim() < 1 or rho1.device != rho2.device:
+        raise ValueError(f"rho1 {tuple(rho1.shape)} on {rho1.device} and rho2 {tuple(rho2.shape)} on {rho2.device} must match, [..., L]")
+    r1 = rho1.to(torch.float64).clamp(0.0, 1.0)
+    r2 = rho2.to(torch.float64).clamp(-1.0, 1.0)
+    kept = r1 >= 1.0
+    rest = torch.where(kept, torch.ones_like(r1), 1.0 - r1 * r1)  # 1 - r1^2, and 1 where it is not used
+    phi2 = ((r2 - r1 * r1) / rest).clamp(-1.0, 1.0)
+    phi2 = torch.where(torch.isnan(rho2) | kept, torch.zeros_like(phi2), phi2)
+    phi1 = torch.where(kept, torch.ones_like(r1), r1 * (1.0 - phi2))
+    gain = torch.where(kept, torch.zeros_like(r1), torch.sqrt((1.0 - phi2 * phi2) * rest))
+    return torch.stack([phi1, phi2, gain], dim=-2).to(torch.float32).contiguous()
+
+
+def _plane_coefficients(coef: np.ndarray, p: int, window: int) -> np.ndarray:
+    """coef [3, L] or [P, 3, L] -> float64 [P, 3, L, L]: every row spread over the modes of fft2's layout"""
+    if coef.shape not in ((3, window), (p, 3, window)):
+        raise ValueError(f"coef must be [3, {window}] or [{p}, 3, {window}], got shape {coef.shape}")
+    return np.broadcast_to(coef, (p, 3, window))[:, :, _radial_bins(window)]
+
+
+def spectral_ar2_reference(z0, zm1, white, coef, window: int):
+    """The specification of `dgmr_spectral_ar2`, in float64 numpy: `spectral_ar_reference` with a second lag.
+
+    z0, white, window, the windows, their classes, the radial bin r(k) and the blend: `spectral_ar_reference`'s.  zm1: fp32 [P, H, W],
+    the frame before z0 in z0's coordinates; coef: fp32 [3, L] = (phi1, phi2, g) (`ar2_coefficients`), or [P, 3, L] for a set per
+    plane, used as passed.  Per window and member: X_0 = fft2(z0 patch), X_-1 = fft2(zm1 patch), A = |X_0| / L and
+      X_t(k) = (phi1[r] X_(t-1)(k) + phi2[r] X_(t-2)(k)) + g[r] A(k) Wh_t(k),   x_t = real(ifft2(X_t)),   t = 1 ... T.
+
+    -> (out float64 [P, M, T, H, W], maj): maj in `spectral_ar_reference`'s layout, from the recursion a rounding error itself
+    follows, per mode:  m_0 = |X_0|, m_-1 = |X_-1|, m_t = |phi1| m_(t-1) + |phi2| m_(t-2) + |g A Wh_t|;  maj_t = ||m_t||_2 / L per
+    window.  (Signed impulse responses would cancel - an AR(2) oscillates - and under-bound the error.)"""
+    window = _check_window(window)
+    z0 = np.asarray(z0, dtype=np.float32).astype(np.float64)
+    zm1 = np.asarray(zm1, dtype=np.float32).astype(np.float64)
+    white = np.asarray(white, dtype=np.float32).astype(np.float64)
+    coef = np.asarray(coef, dtype=np.float32).astype(np.float64)
+    if z0.ndim != 3 or white.ndim != 5 or white.shape[0] != z0.shape[0] or white.shape[3:] != z0.shape[1:] or zm1.shape != z0.shape:
+        raise ValueError(f"z0 and zm1 must be [P, H, W] and white [P, M, T, H, W], got {z0.shape}, {zm1.shape} and {white.shape}")
+    p, m, steps, h, w = white.shape
+    _check_plane(h, w, window)
+    if not 1 <= steps <= MAX_STEPS or m < 1 or p < 1:
+        raise ValueError(f"T={steps} must be 1 ... {MAX_STEPS}, P={p} and M={m} at least 1")
+    ck = _plane_coefficients(coef, p, window)[:, :, None, None, None]  # [P, 3, 1, 1, 1, L, L]
+    phi1, phi2, gain = ck[:, 0], ck[:, 1], ck[:, 2]
+    (ay, hy), (ax, hx) = axis_weights(h, window), axis_weights(w, window)
+    out = np.zeros((p, m, steps, h, w))
+    majorants = []
+    half = window // 2
+    for cy in (0, 1):
+        for cx in (0, 1):
+            ny, nx = h // window - cy, w // window - cx
+            maj = np.zeros((p, m, steps, ny, nx))
+            majorants.append(maj)
+            if ny == 0 or nx == 0:
+                continue
+            ys, xs = slice(cy * half, cy * half + ny * window), slice(cx * half, cx * half + nx * window)
+            wy = (hy if cy else ay)[ys].astype(np.float64)
+            wx = (hx if cx else ax)[xs].astype(np.float64)
+            u = np.fft.fft2(_class_windows(z0, window, cy, cx))[:, None]    # [P, 1, ny, nx, L, L]
+            um = np.fft.fft2(_class_windows(zm1, window, cy, cx))[:, None]
+            amp = gain * np.abs(u) / window
+            wh = np.fft.fft2(_class_windows(white, window, cy, cx))          # [P, M, T, ny, nx, L, L]
+            full = (p, m) + u.shape[2:]
+            x1, x2 = np.broadcast_to(u, full).copy(), np.broadcast_to(um, full).copy()
+            m1, m2 = np.abs(x1), np.abs(x2)
+            for t in range(steps):
+                drive = amp * wh[:, :, t]
+                x1, x2 = (phi1 * x1 + phi2 * x2) + drive, x1
+                m1, m2 = np.abs(phi1) * m1 + np.abs(phi2) * m2 + np.abs(drive), m1
+                maj[:, :, t] = np.sqrt((m1 * m1).sum(axis=(-2, -1))) / window
+                x = np.fft.ifft2(x1).real                                     # [P, M, ny, nx, L, L]
+                x = np.moveaxis(x, -2, -3).reshape(p, m, ny * window, nx * window)
+                out[:, :, t, ys, xs] += x * wy[:, None] * wx[None, :]
+    return out, tuple(majorants)
+
+
+def spectral_ar2(z0: torch.Tensor, zm1: torch.Tensor, white: torch.Tensor, coef: torch.Tensor, window: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`spectral_ar2_reference`'s first result for torch tensors -> fp32 [P, M, T, H, W] on the inputs' device.
+
+    z0, zm1: fp32 [P, H, W] (contiguous planes, any plane stride each); white, out: `spectral_ar`'s layouts and refusals; coef: fp32
+    [3, L] for one set of coefficients, [P, 3, L] for one per plane (`ar2_coefficients`; copied if not contiguous).  On a HIP device one
+    `dgmr_spectral_ar2` on the current stream - all planes in its four launches, also with coefficients per plane -, nothing
+    synchronised; 16-byte accesses where pointers and strides allow them.  On the CPU the float64 reference, rounded."""
+    window = _check_window(window)
+    z0, zs = _planes(z0, "z0")
+    if tuple(zm1.shape) != tuple(z0.shape) or zm1.device != z0.device:
+        raise ValueError(f"zm1 {tuple(zm1.shape)} on {zm1.device} must match z0 {tuple(z0.shape)} on {z0.device}")
+    zm1, zms = _planes(zm1, "zm1")
+    if white.dim() != 5 or white.dtype != torch.float32 or white.shape[0] != z0.shape[0] or tuple(white.shape[3:]) != tuple(z0.shape[1:]) \
+            or white.device != z0.device:
+        raise ValueError(f"white must be a float32 [{z0.shape[0]}, M, T, {z0.shape[1]}, {z0.shape[2]}] tensor on {z0.device}, got "
+                         f"{white.dtype} {tuple(white.shape)} on {white.device}")
+    p, m, steps, h, w = (int(v) for v in white.shape)
+    _check_plane(h, w, window)
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if m < 1 or p < 1:
+        raise ValueError(f"P={p} planes and M={m} members: at least one each is required")
+    if tuple(coef.shape) not in ((3, window), (p, 3, window)) or coef.dtype != torch.float32 or coef.device != z0.device:
+        raise ValueError(f"coef must be a float32 [3, {window}] or [{p}, 3, {window}] tensor on {z0.device}, got {coef.dtype} "
+                         f"{tuple(coef.shape)} on {coef.device}")
+    if out is None:
+        out = torch.empty((p, m, steps, h, w), dtype=torch.float32, device=z0.device)
+    elif tuple(out.shape) != (p, m, steps, h, w) or out.dtype != torch.float32 or out.device != z0.device or _members_layout(out) is None:
+        raise ValueError(f"out must be a float32 [{p}, {m}, {steps}, {h}, {w}] tensor on {z0.device} with contiguous planes and its "
+                         "(P, M) pairs one stride apart")
+    if not z0.is_cuda:
+        ref, _ = spectral_ar2_reference(z0.numpy(), zm1.numpy(), white.numpy(), coef.numpy(), window)
+        out.copy_(torch.from_numpy(ref.astype(np.float32)))
+        return out
+    from ._lib import call
+
+    if _members_layout(white) is None:
+        white = white.contiguous()
+    wms, wss = _members_layout(white)
+    oms, oss = _members_layout(out)
+    coef = coef.contiguous()
+    device = z0.device
+    with torch.cuda.device(device):
+        call("dgmr_spectral_ar2", z0.data_ptr(), zs if p > 1 else 0, zm1.data_ptr(), zms if p > 1 else 0, white.data_ptr(), wms, wss,
+             coef.data_ptr(), 3 * window if coef.dim() == 3 and p > 1 else 0, p, m, steps, h, w, window, out.data_ptr(), oms, oss,
+             _stream(device))
+    return out
+
+
+def estimate_ar2(z: torch.Tensor, field: torch.Tensor, origin: float, spacing: float, window: int, margin: Optional[int] = None,
+                 fallback: Optional[torch.Tensor] = None) -> Ar2Estimate:
+    """`estimate_rho` with the second lag -> Ar2Estimate(rho1 fp32 [P, L], rho2 fp32 [P, L], coef fp32 [P, 3, L], windows float64 [P],
+    previous fp32 [P, H, W]).
+
+    The arguments, the Lagrangian frames, the pool of windows and rho1 are `estimate_rho`'s (the same code: rho1 is its result).
+    rho2[r] = clip(C / sqrt(Pa Pb), -1, 1) from one more `lag_spectra` call, over the K - 2 pairs of frames two apart, pooled over
+    the same windows; NaN where Pa Pb == 0 and everywhere when K = 2 - no fallback: `ar2_coefficients` reads NaN as "no second lag",
+    phi2 = 0, the AR(1) of rho1.  coef = ar2_coefficients(rho1, rho2).  previous: the Lagrangian frame K - 2, the frame before the
+    last moved one step along the field - the recursion's zm1 (a view of the frames).  Nothing synchronises.
+    Near rho1 -> 1 the Yule-Walker solution is ill-conditioned: phi2 = (rho2 - rho1^2) / (1 - rho1^2) moves by d rho2 / (1 - rho1^2)."""
+    frames, weight, fallback = _lagrangian_pool(z, field, origin, spacing, window, margin, fallback)
+    rho1 = _lag1_rho(frames, weight, fallback, window)
+    k, p = int(frames.shape[0]), int(frames.shape[1])
+    if k > 2:
+        gamma, ok = _pooled_coherence(frames, 2, weight, window)
+        rho2 = torch.where(ok, gamma.clamp(-1.0, 1.0), torch.full_like(gamma, float("nan"))).to(torch.float32).contiguous()
+    else:
+        rho2 = torch.full((p, window), float("nan"), dtype=torch.float32, device=frames.device)
+    return Ar2Estimate(rho1, rho2, ar2_coefficients(rho1, rho2), weight.sum(dim=1), frames[k - 2])
 
 
 # ---- probability matching and the precipitation mask -----------------------------------------------------------------------------------
@@ -517,13 +705,23 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     the windows each pool used) and runs one `spectral_ar` per plane.
     probability_matching: match every member and lead time to the last observed dB frame (`probability_match`, in place, before the
     advection); mask_radius (needs the matching): None for no mask, else `precipitation_mask`'s radius in pixels, mask_growth its
-    growth in pixels per lead time.  The defaults leave all three off."""
+    growth in pixels per lead time.  The defaults leave all three off.
+    order: 1 for the AR(1) above; 2 for an AR(2) per mode (`spectral_ar2`), whose second state is the dB frame before the last moved
+    one step along the motion field.  order=2 takes rho="estimate" (`estimate_ar2` per call: `last_rho`, `last_rho2` fp32
+    [planes, window], `last_coef` fp32 [planes, 3, window], `last_windows`) or an fp32 [2, window] tensor (rho1, rho2)
+    (`ar2_coefficients` once: `last_coef` fp32 [3, window]); rho=None is refused - the law has no second lag.  Either way one
+    `spectral_ar2` covers all planes."""
 
     def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
                  min_wet: Optional[int] = None, smooth: int = 2, window: int = 128, threshold: float = 0.1, pad: float = 5.0,
-                 rho: Optional[torch.Tensor] = None, probability_matching: bool = False, mask_radius: Optional[int] = None,
-                 mask_growth: float = 0.0):
+                 rho: Optional[torch.Tensor] = None, order: int = 1, probability_matching: bool = False,
+                 mask_radius: Optional[int] = None, mask_growth: float = 0.0):
         super().__init__(forecast_steps, block, stride, radius, wet_threshold, min_wet, smooth)
+        # order sits beside rho, which it qualifies; a bool here is a positional probability_matching from before it existed
+        if isinstance(order, bool) or order not in (1, 2):
+            raise ValueError(f"order={order!r}: 1 (an AR(1) per mode) or 2 (an AR(2)) is required; pass the arguments after rho by keyword")
+        self.order = int(order)
+        self.last_rho2 = self.last_coef = None
         self.probability_matching = bool(probability_matching)
         if mask_radius is not None and not self.probability_matching:
             raise ValueError("mask_radius needs probability_matching=True: a masked-out element is dry only after the matching")
@@ -536,10 +734,17 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         self.estimate = isinstance(rho, str)
         if self.estimate and rho != "estimate":
             raise ValueError(f"rho={rho!r}: a tensor, None or \"estimate\" is required")
+        if self.order == 2 and rho is None:
+            raise ValueError("order=2 needs rho=\"estimate\" or a [2, window] tensor (rho1, rho2): the fixed law has no second lag, and "
+                             "rho2 = rho1^2 would be the AR(1) at twice the state")
         rho = lifetime_rho(self.window) if rho is None or self.estimate else torch.as_tensor(rho, dtype=torch.float32)
-        if tuple(rho.shape) != (self.window,):
+        if self.order == 2 and not self.estimate:
+            if tuple(rho.shape) != (2, self.window):
+                raise ValueError(f"order=2: rho must be [2, {self.window}] = (rho1, rho2), got shape {tuple(rho.shape)}")
+            self.coef = ar2_coefficients(rho[0], rho[1])  # fp32 [3, window]
+        elif tuple(rho.shape) != (self.window,):
             raise ValueError(f"rho must hold {self.window} values, got shape {tuple(rho.shape)}")
-        self.rho = rho  # with rho="estimate": the fallback of `estimate_rho`
+        self.rho = rho  # with rho="estimate": the fallback of `estimate_rho`; with order=2 and a tensor: (rho1, rho2)
         self.last_rho = self.last_windows = None
 
     def white_noise(self, planes: int, num_members: int, h: int, w: int, device, seed: int = 0) -> torch.Tensor:
@@ -563,7 +768,16 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         self.last_field = motion_field(context[-CONTEXT_FRAMES:], **self.params)
         origin, spacing = lattice_geometry(self.params["block"], self.params["stride"])
         z0 = to_db(context[-1], self.threshold, self.pad)
-        if self.estimate:
+        if self.order == 2:
+            if self.estimate:
+                est = estimate_ar2(to_db(context[-CONTEXT_FRAMES:], self.threshold, self.pad), self.last_field, origin, spacing,
+                                   self.window, fallback=self.rho)
+                self.last_rho, self.last_rho2, self.last_coef, self.last_windows, zm1 = est
+            else:
+                self.last_coef = self.coef.to(context.device)
+                zm1 = advect(to_db(context[-2], self.threshold, self.pad), self.last_field, 1, origin, spacing)[:, -1]
+            z = spectral_ar2(z0, zm1, white, self.last_coef, self.window)  # one call for all planes, coefficients per plane or not
+        elif self.estimate:
             est = estimate_rho(to_db(context[-CONTEXT_FRAMES:], self.threshold, self.pad), self.last_field, origin, spacing, self.window,
                                fallback=self.rho)
             self.last_rho, self.last_windows = est

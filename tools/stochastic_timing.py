@@ -1,7 +1,7 @@
 """Device time of the stochastic advection ensemble on a full 1536 x 1280 composite (skillful_nowcasting_amd/stochastic.py;
 dgmr_spectral_ar in csrc/spectrum.hip, dgmr_advect_series in csrc/advect.hip).
 
-    python tools/stochastic_timing.py [--repeats 7] [--out profiles/stochastic_timing.json]
+    python tools/stochastic_timing.py [--repeats 7] [--order 2] [--out profiles/stochastic_timing.json]
                                       [--match-out profiles/probability_match_timing.json]
 
 Inputs: the rain-covered sequence of tools/advection_timing.py (a smooth field moving by (2, -3) pixels per frame), M = 8 members,
@@ -20,6 +20,10 @@ With --match-out also (dgmr_probability_match in csrc/probmatch.hip), written to
   * the same ranks by a full sort on the device (argsort of every plane, the sorted target scattered through it), for scale, and
     how much of the two results differs (a binned rank is off by less than a bin's occupancy; ties are ordered arbitrarily by a sort);
   * the whole nowcast without matching, with it, and with it and a mask.
+With --order 2 also (dgmr_spectral_ar2 in csrc/spectrum.hip), in the --out file:
+  * spectral_ar2 beside spectral_ar on the same inputs (zm1: the frame before the last moved one step; rho2 = rho^3), and the
+    same recursion written with torch.fft;
+  * the whole nowcast at order 2 beside order 1, with explicit correlations and with rho="estimate".
 Numbers are recorded, not asserted."""
 import argparse
 import json
@@ -88,6 +92,44 @@ def spectral_ar_torch(z0, white, rho, window):
     return out
 
 
+def spectral_ar2_torch(z0, zm1, white, coef, window):
+    """stochastic.spectral_ar2_reference with torch.fft in fp32 on the tensors' device (half spectra: the fields are real)."""
+    import numpy as np
+    import torch
+
+    from skillful_nowcasting_amd.spectra import _radial_bins
+    from skillful_nowcasting_amd.stochastic import axis_weights
+
+    p, m, steps, h, w = white.shape
+    dev = z0.device
+    bins = torch.from_numpy(_radial_bins(window)[:, :window // 2 + 1].copy()).to(dev)
+    phi1, phi2, gain = coef[0][bins], coef[1][bins], coef[2][bins]
+    (ay, hy), (ax, hx) = axis_weights(h, window), axis_weights(w, window)
+    out = torch.zeros((p, m, steps, h, w), dtype=torch.float32, device=dev)
+    half = window // 2
+    for cy in (0, 1):
+        for cx in (0, 1):
+            ny, nx = h // window - cy, w // window - cx
+            if ny == 0 or nx == 0:
+                continue
+            ys, xs = slice(cy * half, cy * half + ny * window), slice(cx * half, cx * half + nx * window)
+            wgt = torch.from_numpy(np.outer((hy if cy else ay)[ys], (hx if cx else ax)[xs])).to(dev)
+
+            def windows(x):
+                t = x[..., ys, xs]
+                return t.reshape(x.shape[:-2] + (ny, window, nx, window)).movedim(-3, -2)
+
+            u = torch.fft.rfft2(windows(z0))[:, None]
+            amp = gain * (u.abs() / window)
+            x1 = u.expand(p, m, ny, nx, window, half + 1).clone()
+            x2 = torch.fft.rfft2(windows(zm1))[:, None].expand(p, m, ny, nx, window, half + 1).clone()
+            for t in range(steps):
+                x1, x2 = (phi1 * x1 + phi2 * x2) + amp * torch.fft.rfft2(windows(white[:, :, t])), x1
+                x = torch.fft.irfft2(x1, s=(window, window)).movedim(-2, -3).reshape(p, m, ny * window, nx * window)
+                out[:, :, t, ys, xs] += x * wgt
+    return out
+
+
 def rank_match_torch(z, target):
     """Exact rank matching with torch: every plane sorted in full, the sorted target scattered through the order."""
     import torch
@@ -104,6 +146,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--match-out", default=None)
+    ap.add_argument("--order", type=int, default=1, choices=(1, 2))
     a = ap.parse_args()
     import torch
 
@@ -118,7 +161,8 @@ def main():
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev).manual_seed(0)
     seq = rain_sequence(gen, dev, 4, (2, -3), False)  # [4, H, W]
-    rec = {"device": torch.cuda.get_device_name(0), "command": f"python tools/stochastic_timing.py --repeats {a.repeats}", "frame": [H, W],
+    rec = {"device": torch.cuda.get_device_name(0),
+           "command": f"python tools/stochastic_timing.py --repeats {a.repeats}" + (" --order 2" if a.order == 2 else ""), "frame": [H, W],
            "members": MEMBERS, "lead_times": T_OUT, "window": WINDOW, "assumed_rates": {"copy_bytes_per_s": COPY_BYTES_PER_S},
            "wet_pixel_share": float((seq > 0).double().mean())}
     nowcaster = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW)
@@ -151,6 +195,35 @@ def main():
         print(f"torch.fft on the device is not available: {rec['spectral_ar_torch_fft']['unavailable']}", flush=True)
     field = motion_field(seq[:, None], 32, 16, 8)
     origin, spacing = lattice_geometry(32, 16)
+    rhos = None
+    if a.order == 2:
+        from skillful_nowcasting_amd.advection import advect
+        from skillful_nowcasting_amd.stochastic import ar2_coefficients, spectral_ar2
+
+        # a second lag that forgets faster than the AR(1) of rho would (rho2 = rho^3 < rho^2: phi2 < 0); the values do not enter the time
+        rhos = torch.stack([rho, rho ** 3])
+        coef = ar2_coefficients(rhos[0], rhos[1])
+        zm1 = advect(to_db(seq[-2:-1]), field, 1, origin, spacing)[:, -1]
+        out2 = torch.empty_like(out)
+        ar2 = timed(lambda: spectral_ar2(z0, zm1, white, coef, WINDOW, out=out2), a.repeats)
+        ar2.update({"windows": windows, "transforms_2d": windows * (2 * T_OUT + 2), "bytes_moved": nbytes, "GB_per_s": nbytes / ar2["ms"] / 1e6,
+                    "over_spectral_ar": ar2["ms"] / ar["ms"]})
+        rec["spectral_ar2"] = ar2
+        print(f"spectral_ar2 M={MEMBERS} T={T_OUT} L={WINDOW}: {ar2['ms']:.3f} ms ({ar2['min_ms']:.3f} - {ar2['max_ms']:.3f}), "
+              f"{ar2['over_spectral_ar']:.2f} x spectral_ar", flush=True)
+        try:
+            ref = spectral_ar2_torch(z0, zm1, white, coef, WINDOW)
+            gap = float((ref - out2).abs().max())
+            tf = timed(lambda: spectral_ar2_torch(z0, zm1, white, coef, WINDOW), max(3, a.repeats // 2))
+            tf["max_abs_difference_to_kernel"] = gap
+            tf["over_kernel"] = tf["ms"] / ar2["ms"]
+            rec["spectral_ar2_torch_fft"] = tf
+            print(f"torch.fft AR(2) recursion: {tf['ms']:.3f} ms ({tf['over_kernel']:.1f} x the kernel), largest difference {gap:.3e}", flush=True)
+            del ref
+        except RuntimeError as e:  # no FFT library on the device
+            rec["spectral_ar2_torch_fft"] = {"unavailable": str(e).splitlines()[0]}
+            print(f"torch.fft on the device is not available: {rec['spectral_ar2_torch_fft']['unavailable']}", flush=True)
+        del out2, zm1
     moved = torch.empty(MEMBERS, T_OUT, H, W, device=dev)
     adv = timed(lambda: advect_series(out[0], field, origin, spacing, field_group=MEMBERS, out=moved), a.repeats)
     adv.update({"bytes_stored": plane, "GB_per_s_stored": plane / adv["ms"] / 1e6, "ms_at_copy_rate": 2 * plane / COPY_BYTES_PER_S * 1e3})
@@ -183,6 +256,14 @@ def main():
     frames = seq[..., None].contiguous()
     rec["nowcast"] = timed(lambda: nowcaster.nowcast(frames, MEMBERS, seed=1), a.repeats)
     print(f"whole nowcast: {rec['nowcast']['ms']:.3f} ms", flush=True)
+    if a.order == 2:
+        for key, kw in (("nowcast_order2", {"rho": rhos.cpu(), "order": 2}), ("nowcast_estimate", {"rho": "estimate"}),
+                        ("nowcast_order2_estimate", {"rho": "estimate", "order": 2})):
+            nc = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW, **kw)
+            rec[key] = timed(lambda: nc.nowcast(frames, MEMBERS, seed=1), a.repeats)
+            print(f"whole {key}: {rec[key]['ms']:.3f} ms", flush=True)
+        rec["nowcast_order2"]["over_order1"] = rec["nowcast_order2"]["ms"] / rec["nowcast"]["ms"]
+        rec["nowcast_order2_estimate"]["over_order1"] = rec["nowcast_order2_estimate"]["ms"] / rec["nowcast_estimate"]["ms"]
     if match is not None:
         match["nowcast"] = rec["nowcast"]
         for key, kw in (("nowcast_matched", {}), ("nowcast_matched_masked", {"mask_radius": 8})):
