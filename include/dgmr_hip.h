@@ -702,7 +702,7 @@ int dgmr_advect(const float* x, int64_t x_plane_stride, const float* field, int6
                 int Gx, float origin, float spacing, int T, float* out, int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The stochastic advection ensemble (stochastic.py; csrc/spectrum.hip, csrc/advect.hip).  New symbols, same ABI version.
+ * The stochastic advection ensemble (stochastic.py; csrc/spectral_ar.hip, csrc/advect.hip).  New symbols, same ABI version.
  *
  * dgmr_spectral_ar: an AR(1) process per Fourier mode of overlapping L x L windows, L one of 32, 64, 128, blended to full planes.
  * z0: P fp32 planes [H][W], z0_plane_stride apart, any real values (no missing-value rule).  white: plane n = p M + m of lead time t
@@ -763,7 +763,7 @@ int dgmr_lag_spectra(const float* a, int64_t a_plane_stride, const float* b, int
 
 /* ------------------------------------------------------------------------------------------------
  * dgmr_spectral_ar2: dgmr_spectral_ar with a second lag (stochastic.py: spectral_ar2, ar2_coefficients, estimate_ar2;
- * csrc/spectrum.hip).  New symbol, same ABI version.
+ * csrc/spectral_ar.hip).  New symbol, same ABI version.
  * z0, white, out, P, M, T, H, W, L, the windows, their classes, the radial bin r(k), the blend and the four launches are
  * dgmr_spectral_ar's.  zm1: the frame before z0 in z0's coordinates, P fp32 planes [H][W], zm1_plane_stride apart.  coef: per plane
  * three rows of L fp32 values (phi1[r], phi2[r], g[r]), plane p at coef + p coef_plane_stride; coef_plane_stride = 0 is one set for

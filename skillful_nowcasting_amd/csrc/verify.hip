@@ -18,6 +18,11 @@
 // are exact in any order: waves count with ballots (the rank table: the key of the wave's first present lane by ballot, every
 // other key lane by lane), add to LDS counters and the workgroup adds its non-zero counters to the outputs
 // with integer atomics.
+//
+// Exceedance table (value.py: dgmr_exceedance_table), from which reliability, Brier score, ROC points and economic value are derived.
+// One streaming read (16-byte loads) of the ensemble and the observation; per pixel and threshold the number of members that reach the
+// threshold is the row, the observation's own exceedance the column of a per-workgroup histogram in LDS (at most 8 x 33 x 2
+// counters).  A wave adds the key of its first present lane once by ballot - in a radar field that is nearly everybody's key - and the other keys lane by lane; the workgroup adds its non-zero counters to the table with integer atomics.
 #include "common.h"
 
 namespace {
@@ -357,6 +362,69 @@ int ens_check_shape(const char* fn, int M, int64_t N, int H, int W) {
     return 0;
 }
 
+// ---- exceedance table ----------------------------------------------------------------------------------------------------------------
+constexpr int EXC_MAX_M = 32, EXC_MAX_K = 8, EXC_THREADS = 256, EXC_TARGET_BLOCKS = 4096;
+
+inline int exc_blocks_per_plane(int64_t N, int64_t quads) {
+    const int64_t want = std::max<int64_t>(1, EXC_TARGET_BLOCKS / N);
+    return (int)std::min<int64_t>(want, (quads + EXC_THREADS - 1) / EXC_THREADS);
+}
+
+// quads = H * W / 4 is a multiple of 64 (H and W are multiples of 16): a wave is inside the plane as a whole or not at all.
+__global__ __launch_bounds__(EXC_THREADS) void exceedance_kernel(const float* __restrict__ fc, int64_t mstride, const float* __restrict__ obs,
+                                                                 int M, int64_t quads, int BPP, const float* __restrict__ thr, int K,
+                                                                 unsigned long long* __restrict__ table) {
+    __shared__ unsigned int s_hist[EXC_MAX_K * (EXC_MAX_M + 1) * 2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n_hist = K * (M + 1) * 2;
+    for (int i = tid; i < n_hist; i += EXC_THREADS) s_hist[i] = 0;
+    float tk[EXC_MAX_K];
+#pragma unroll
+    for (int k = 0; k < EXC_MAX_K; ++k) tk[k] = k < K ? thr[k] : __builtin_inff();
+    __syncthreads();
+    const int64_t n = blockIdx.x / BPP;
+    const int b = (int)(blockIdx.x - n * BPP);
+    const f32x4* __restrict__ obs_n = (const f32x4*)(obs + n * quads * 4);
+    const float* __restrict__ fc_n = fc + n * quads * 4;
+    for (int64_t i = (int64_t)b * EXC_THREADS + tid; i < quads; i += (int64_t)BPP * EXC_THREADS) {
+        const f32x4 yv = obs_n[i];
+        const float y[4] = {yv.x, yv.y, yv.z, yv.w};
+        int cnt[EXC_MAX_K][4];
+#pragma unroll
+        for (int k = 0; k < EXC_MAX_K; ++k)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) cnt[k][p] = 0;
+#pragma unroll 4
+        for (int m = 0; m < M; ++m) {
+            const f32x4 xv = *(const f32x4*)(fc_n + m * mstride + i * 4);
+            const float x[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+            for (int k = 0; k < EXC_MAX_K; ++k)
+#pragma unroll
+                for (int p = 0; p < 4; ++p) cnt[k][p] += x[p] >= tk[k] ? 1 : 0;
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const bool pres = y[p] >= 0.f;
+            const unsigned long long P = __ballot(pres);
+            if (!P) continue;  // (wave-uniform)
+            const int leader = __ffsll((long long)P) - 1;
+#pragma unroll
+            for (int k = 0; k < EXC_MAX_K; ++k) {
+                if (k >= K) break;  // (uniform)
+                const int key = (k * (M + 1) + cnt[k][p]) * 2 + (y[p] >= tk[k] ? 1 : 0);  // < n_hist: cnt <= M
+                const int k0 = __builtin_amdgcn_readlane(key, leader);
+                const unsigned long long same = __ballot(pres && key == k0);
+                if (lane == leader) atomicAdd(&s_hist[k0], (unsigned int)__popcll(same));
+                if (pres && key != k0) atomicAdd(&s_hist[key], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_hist; i += EXC_THREADS)
+        if (s_hist[i]) atomicAdd(&table[n * n_hist + i], (unsigned long long)s_hist[i]);
+}
+
 }  // namespace
 
 extern "C" int64_t dgmr_ensemble_scores_workspace(int M, int64_t N, int H, int W) {
@@ -424,6 +492,33 @@ extern "C" int dgmr_ensemble_scores(const float* forecast, int64_t member_stride
 #undef ENS_GO
     hipLaunchKernelGGL(ens_finalize_kernel, dim3(cdiv(N * ENS_Q, ENS_WAVES)), dim3(64 * ENS_WAVES), 0, st, (const double*)workspace, N, BPP, M,
                        lvl_slot, S, abs_err, pair);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_exceedance_table(const float* forecast, int64_t member_stride, const float* observed, int M, int64_t N, int H, int W,
+                                     const float* thresholds, int K, int64_t* table, void* stream) {
+    const char* fn = "dgmr_exceedance_table";
+    DGMR_CHECK_ARG(M >= 1 && M <= EXC_MAX_M, "%s: M=%d members, 1 ... %d are supported", fn, M, EXC_MAX_M);
+    DGMR_CHECK_ARG(N >= 1 && N <= (1 << 24), "%s: N=%lld planes out of range", fn, (long long)N);
+    DGMR_CHECK_ARG(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "%s: H=%d and W=%d must be positive multiples of 16", fn, H, W);
+    DGMR_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(K >= 0 && K <= EXC_MAX_K, "%s: K=%d thresholds, at most %d are supported", fn, K, EXC_MAX_K);
+    DGMR_CHECK_ARG(forecast && observed && ((thresholds && table) || K == 0), "%s: null pointer", fn);
+    DGMR_CHECK_ARG(M == 1 || (member_stride >= 0 && member_stride % 4 == 0 && member_stride <= INT64_MAX / 4 / EXC_MAX_M),
+                   "%s: member_stride=%lld must be a non-negative multiple of 4 elements", fn, (long long)member_stride);
+    DGMR_CHECK_ARG((((uintptr_t)forecast | (uintptr_t)observed) & 15) == 0, "%s: forecast and observed must be 16-byte aligned", fn);
+    DGMR_CHECK_ARG(((uintptr_t)table & 7) == 0, "%s: table must be 8-byte aligned", fn);
+    if (K == 0) return 0;  // an empty table
+    hipStream_t st = ST;
+    if (hipMemsetAsync(table, 0, (size_t)N * K * (M + 1) * 2 * sizeof(int64_t), st) != hipSuccess) {
+        dgmr_set_error("%s: clearing the table failed: %s", fn, hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    const int64_t quads = (int64_t)H * W / 4;
+    const int BPP = exc_blocks_per_plane(N, quads);
+    hipLaunchKernelGGL(exceedance_kernel, dim3((unsigned)(N * BPP)), dim3(EXC_THREADS), 0, st, forecast, M == 1 ? 0 : member_stride, observed,
+                       M, quads, BPP, thresholds, K, (unsigned long long*)table);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

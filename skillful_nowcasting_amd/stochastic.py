@@ -15,7 +15,7 @@
     coordinates first, advection last) and taken back to rain rates (`from_db`).
 
 `spectral_ar_reference` is the specification in float64 numpy.  On a HIP device `spectral_ar` is `dgmr_spectral_ar`
-(csrc/spectrum.hip) on the current stream, without synchronisation; CPU tensors go through the reference.
+(csrc/spectral_ar.hip) on the current stream, without synchronisation; CPU tensors go through the reference.
 `probability_match_reference` is the specification of the matching in fp32 numpy, which `dgmr_probability_match`
 (csrc/probmatch.hip) reproduces bit for bit: ranks from a 4096-bin histogram of each plane instead of a sort.
 
@@ -188,16 +188,8 @@ def _members_layout(t: torch.Tensor):
     return ms, ss
 
 
-def spectral_ar(z0: torch.Tensor, white: torch.Tensor, rho: torch.Tensor, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`spectral_ar_reference`'s first result for torch tensors -> fp32 [P, M, T, H, W] on the inputs' device.
-
-    z0: fp32 [P, H, W] (contiguous planes, any plane stride); white: fp32 [P, M, T, H, W]; rho: fp32 [L].  white and out (an fp32
-    [P, M, T, H, W] tensor or view) must have contiguous planes, steps at least H * W apart and the (P, M) pairs one stride apart - a
-    slice of a larger buffer over T, H-aligned rows or members is written in place; a white of another layout is copied, an out of
-    another layout is refused.  On a HIP device one `dgmr_spectral_ar` on the current stream, nothing synchronised; 16-byte accesses
-    where pointers and strides allow them.  On the CPU the float64 reference, rounded."""
-    window = _check_window(window)
-    z0, zs = _planes(z0, "z0")
+def _check_white(z0: torch.Tensor, white: torch.Tensor, window: int):
+    """white against z0 [P, H, W] (`_planes`' result) and the window -> (P, M, T, H, W)"""
     if white.dim() != 5 or white.dtype != torch.float32 or white.shape[0] != z0.shape[0] or tuple(white.shape[3:]) != tuple(z0.shape[1:]) \
             or white.device != z0.device:
         raise ValueError(f"white must be a float32 [{z0.shape[0]}, M, T, {z0.shape[1]}, {z0.shape[2]}] tensor on {z0.device}, got "
@@ -208,22 +200,48 @@ def spectral_ar(z0: torch.Tensor, white: torch.Tensor, rho: torch.Tensor, window
         raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
     if m < 1 or p < 1:
         raise ValueError(f"P={p} planes and M={m} members: at least one each is required")
+    return p, m, steps, h, w
+
+
+def _check_out(out: Optional[torch.Tensor], shape, device) -> torch.Tensor:
+    """out as passed if it is an fp32 tensor or view of `shape` = (P, M, T, H, W) on `device` that `_members_layout` takes; a new
+    tensor for None"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != device or _members_layout(out) is None:
+        raise ValueError(f"out must be a float32 [{', '.join(str(v) for v in shape)}] tensor on {device} with contiguous planes and its "
+                         "(P, M) pairs one stride apart")
+    return out
+
+
+def _strided(t: torch.Tensor):
+    """[P, M, T, H, W] as the device entries read it -> (t, member stride, step stride): copied where `_members_layout` refuses it"""
+    if _members_layout(t) is None:
+        t = t.contiguous()
+    return (t,) + _members_layout(t)
+
+
+def spectral_ar(z0: torch.Tensor, white: torch.Tensor, rho: torch.Tensor, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`spectral_ar_reference`'s first result for torch tensors -> fp32 [P, M, T, H, W] on the inputs' device.
+
+    z0: fp32 [P, H, W] (contiguous planes, any plane stride); white: fp32 [P, M, T, H, W]; rho: fp32 [L].  white and out (an fp32
+    [P, M, T, H, W] tensor or view) must have contiguous planes, steps at least H * W apart and the (P, M) pairs one stride apart - a
+    slice of a larger buffer over T, H-aligned rows or members is written in place; a white of another layout is copied, an out of
+    another layout is refused.  On a HIP device one `dgmr_spectral_ar` on the current stream, nothing synchronised; 16-byte accesses
+    where pointers and strides allow them.  On the CPU the float64 reference, rounded."""
+    window = _check_window(window)
+    z0, zs = _planes(z0, "z0")
+    p, m, steps, h, w = _check_white(z0, white, window)
     if rho.dim() != 1 or rho.shape[0] != window or rho.dtype != torch.float32 or rho.device != z0.device:
         raise ValueError(f"rho must be a float32 [{window}] tensor on {z0.device}, got {rho.dtype} {tuple(rho.shape)} on {rho.device}")
-    if out is None:
-        out = torch.empty((p, m, steps, h, w), dtype=torch.float32, device=z0.device)
-    elif tuple(out.shape) != (p, m, steps, h, w) or out.dtype != torch.float32 or out.device != z0.device or _members_layout(out) is None:
-        raise ValueError(f"out must be a float32 [{p}, {m}, {steps}, {h}, {w}] tensor on {z0.device} with contiguous planes and its "
-                         "(P, M) pairs one stride apart")
+    out = _check_out(out, (p, m, steps, h, w), z0.device)
     if not z0.is_cuda:
         ref, _ = spectral_ar_reference(z0.numpy(), white.numpy(), rho.numpy(), window)
         out.copy_(torch.from_numpy(ref.astype(np.float32)))
         return out
     from ._lib import call
 
-    if _members_layout(white) is None:
-        white = white.contiguous()
-    wms, wss = _members_layout(white)
+    white, wms, wss = _strided(white)
     oms, oss = _members_layout(out)
     device = z0.device
     with torch.cuda.device(device):
@@ -498,33 +516,18 @@ def spectral_ar2(z0: torch.Tensor, zm1: torch.Tensor, white: torch.Tensor, coef:
     if tuple(zm1.shape) != tuple(z0.shape) or zm1.device != z0.device:
         raise ValueError(f"zm1 {tuple(zm1.shape)} on {zm1.device} must match z0 {tuple(z0.shape)} on {z0.device}")
     zm1, zms = _planes(zm1, "zm1")
-    if white.dim() != 5 or white.dtype != torch.float32 or white.shape[0] != z0.shape[0] or tuple(white.shape[3:]) != tuple(z0.shape[1:]) \
-            or white.device != z0.device:
-        raise ValueError(f"white must be a float32 [{z0.shape[0]}, M, T, {z0.shape[1]}, {z0.shape[2]}] tensor on {z0.device}, got "
-                         f"{white.dtype} {tuple(white.shape)} on {white.device}")
-    p, m, steps, h, w = (int(v) for v in white.shape)
-    _check_plane(h, w, window)
-    if not 1 <= steps <= MAX_STEPS:
-        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
-    if m < 1 or p < 1:
-        raise ValueError(f"P={p} planes and M={m} members: at least one each is required")
+    p, m, steps, h, w = _check_white(z0, white, window)
     if tuple(coef.shape) not in ((3, window), (p, 3, window)) or coef.dtype != torch.float32 or coef.device != z0.device:
         raise ValueError(f"coef must be a float32 [3, {window}] or [{p}, 3, {window}] tensor on {z0.device}, got {coef.dtype} "
                          f"{tuple(coef.shape)} on {coef.device}")
-    if out is None:
-        out = torch.empty((p, m, steps, h, w), dtype=torch.float32, device=z0.device)
-    elif tuple(out.shape) != (p, m, steps, h, w) or out.dtype != torch.float32 or out.device != z0.device or _members_layout(out) is None:
-        raise ValueError(f"out must be a float32 [{p}, {m}, {steps}, {h}, {w}] tensor on {z0.device} with contiguous planes and its "
-                         "(P, M) pairs one stride apart")
+    out = _check_out(out, (p, m, steps, h, w), z0.device)
     if not z0.is_cuda:
         ref, _ = spectral_ar2_reference(z0.numpy(), zm1.numpy(), white.numpy(), coef.numpy(), window)
         out.copy_(torch.from_numpy(ref.astype(np.float32)))
         return out
     from ._lib import call
 
-    if _members_layout(white) is None:
-        white = white.contiguous()
-    wms, wss = _members_layout(white)
+    white, wms, wss = _strided(white)
     oms, oss = _members_layout(out)
     coef = coef.contiguous()
     device = z0.device
@@ -642,11 +645,7 @@ def probability_match(z: torch.Tensor, target: torch.Tensor, mask: Optional[torc
                              or mask.shape[1] not in (1, steps) or tuple(mask.shape[2:]) != (h, w)):
         raise ValueError(f"mask must be a uint8 [{p}, 1 or {steps}, {h}, {w}] tensor on {z.device}, got {mask.dtype} {tuple(mask.shape)} on "
                          f"{mask.device}")
-    if out is None:
-        out = torch.empty((p, m, steps, h, w), dtype=torch.float32, device=z.device)
-    elif tuple(out.shape) != (p, m, steps, h, w) or out.dtype != torch.float32 or out.device != z.device or _members_layout(out) is None:
-        raise ValueError(f"out must be a float32 [{p}, {m}, {steps}, {h}, {w}] tensor on {z.device} with contiguous planes and its "
-                         "(P, M) pairs one stride apart")
+    out = _check_out(out, (p, m, steps, h, w), z.device)
     target_sorted = torch.sort(target.reshape(p, n), dim=1).values
     if not z.is_cuda:
         ref = probability_match_reference(z.numpy(), target_sorted.numpy(), None if mask is None else mask.numpy(), lo, scale)
@@ -654,9 +653,7 @@ def probability_match(z: torch.Tensor, target: torch.Tensor, mask: Optional[torc
         return out
     from ._lib import call, load
 
-    if _members_layout(z) is None:
-        z = z.contiguous()
-    zms, zss = _members_layout(z)
+    z, zms, zss = _strided(z)
     oms, oss = _members_layout(out)
     mask_ptr = mask_ps = mask_ss = 0
     if mask is not None:

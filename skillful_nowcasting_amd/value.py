@@ -5,7 +5,7 @@ missing when `!(y >= 0)`, as everywhere in the verification), `table[j][o]` coun
 and the observation is (`o = 1`) or is not (`o = 0`) `>= thr`.  The ensemble's forecast probability at such a pixel is j / M.
 
 `exceedance_table_reference` is the specification in numpy.  On a HIP device `exceedance_table` is `dgmr_exceedance_table`
-(csrc/spectrum.hip): one streaming read of the ensemble and the observation, integer counts, exact.  `ValueVerifier` accumulates the
+(csrc/verify.hip): one streaming read of the ensemble and the observation, integer counts, exact.  `ValueVerifier` accumulates the
 tables per lead time on the device, weighted by the cases' inverse inclusion probabilities, and has `NowcastVerifier`'s `update`, so
 `DGMR.verify_batch(batch, ValueVerifier(...))` works; `compute()` turns the sums into the metrics on the host.  Grid scale only: no
 pooled-scale economic value.

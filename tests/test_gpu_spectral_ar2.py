@@ -1,4 +1,4 @@
-"""The AR(2) recursion of the stochastic ensemble on the GPU: dgmr_spectral_ar2 (csrc/spectrum.hip) against the float64 specification
+"""The AR(2) recursion of the stochastic ensemble on the GPU: dgmr_spectral_ar2 (csrc/spectral_ar.hip) against the float64 specification
 of stochastic.py on the same arrays, its reductions to the AR(1) kernel and to a swap of its two states, determinism, `estimate_ar2`
 against its CPU path and the nowcaster with order=2 end to end.  No test has a time threshold."""
 import ctypes

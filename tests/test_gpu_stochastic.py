@@ -1,4 +1,4 @@
-"""The stochastic advection ensemble on the GPU: dgmr_spectral_ar (csrc/spectrum.hip) and dgmr_advect_series (csrc/advect.hip) against
+"""The stochastic advection ensemble on the GPU: dgmr_spectral_ar (csrc/spectral_ar.hip) and dgmr_advect_series (csrc/advect.hip) against
 the float64 specifications of stochastic.py / advection.py on the same arrays, the nowcaster end to end against its CPU path, and its
 members in the three verifiers.  No test has a time threshold."""
 import ctypes

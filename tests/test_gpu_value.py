@@ -1,4 +1,4 @@
-"""Exceedance tables on the GPU: dgmr_exceedance_table (csrc/spectrum.hip) against value.exceedance_table_reference on the same arrays,
+"""Exceedance tables on the GPU: dgmr_exceedance_table (csrc/verify.hip) against value.exceedance_table_reference on the same arrays,
 exactly, and ValueVerifier's device accumulator.  No test has a time threshold."""
 import functools
 

@@ -1,5 +1,5 @@
 """Device time of the stochastic advection ensemble on a full 1536 x 1280 composite (skillful_nowcasting_amd/stochastic.py;
-dgmr_spectral_ar in csrc/spectrum.hip, dgmr_advect_series in csrc/advect.hip).
+dgmr_spectral_ar in csrc/spectral_ar.hip, dgmr_advect_series in csrc/advect.hip).
 
     python tools/stochastic_timing.py [--repeats 7] [--order 2] [--out profiles/stochastic_timing.json]
                                       [--match-out profiles/probability_match_timing.json]
@@ -20,7 +20,7 @@ With --match-out also (dgmr_probability_match in csrc/probmatch.hip), written to
   * the same ranks by a full sort on the device (argsort of every plane, the sorted target scattered through it), for scale, and
     how much of the two results differs (a binned rank is off by less than a bin's occupancy; ties are ordered arbitrarily by a sort);
   * the whole nowcast without matching, with it, and with it and a mask.
-With --order 2 also (dgmr_spectral_ar2 in csrc/spectrum.hip), in the --out file:
+With --order 2 also (dgmr_spectral_ar2 in csrc/spectral_ar.hip), in the --out file:
   * spectral_ar2 beside spectral_ar on the same inputs (zm1: the frame before the last moved one step; rho2 = rho^3), and the
     same recursion written with torch.fft;
   * the whole nowcast at order 2 beside order 1, with explicit correlations and with rho="estimate".
