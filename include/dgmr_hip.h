@@ -283,18 +283,13 @@ int dgmr_sn_wgrad_finalize(const float* g, float* gw, float* dot, const float* i
 int dgmr_spectral_sigma(const float* w, float* u, float* v, float* u_save, float* v_save, float* inv_sigma,
                         float* scratch, float* tmp /* [Cout + K] */, int Cout, int Cin, int taps, float eps, int train,
                         void* stream);
-/* T consecutive train-mode calls of ONE module (a sampler conv is called once per forecast step, a discriminator conv once
- * per frame: generators.py:153-178, discriminators.py:119-133,201-226) in one go.  gram = W W^T [Cout][Cout] (computed by the
- * caller with dgmr_conv_fwd on the [Cout][K] weight matrix, valid until W changes): the T dependent power iterations then
- * run on gram alone and W is read twice instead of 2T times.  Outputs per call t: inv_sigma[t], u_hist[t][Cout],
- * v_hist[t][K] (the vectors sigma_t was computed with); u, v are left at their values after call T.  T <= 32.
- * tmp: [Cout + T] floats; scratch as above. */
-int dgmr_spectral_sigma_seq(const float* w, const float* gram, float* u, float* v, float* u_hist, float* v_hist,
-                            float* inv_sigma, float* scratch, float* tmp, int Cout, int Cin, int taps, float eps, int T,
-                            void* stream);
 
-/* The same for many modules at once: every spectral-norm call sequence of one generator / discriminator forward in three
- * launches (the iterations do not depend on activations; the chains of all modules run concurrently, one workgroup each).
+/* The T consecutive train-mode calls of a module (a sampler conv is called once per forecast step, a discriminator conv once
+ * per frame: generators.py:153-178, discriminators.py:119-133,201-226) in one go, for many modules at once: every spectral-norm
+ * call sequence of one generator / discriminator forward (the iterations do not depend on activations).  gram = W W^T
+ * [Cout][Cout] (computed by the caller with dgmr_conv_fwd on the [Cout][K] weight matrix, valid until W changes): the T dependent
+ * power iterations then run on gram alone and W is read twice instead of 2T times.  Outputs per call t: inv_sigma[t],
+ * u_hist[t][Cout], v_hist[t][K] (the vectors sigma_t was computed with); u, v are left at their values after call T.
  * descs: DEVICE array of n descriptors.  Outputs live in one caller-allocated float arena (offsets in floats):
  * inv_sigma[T], u_hist[T][Cout], v_hist[T][K], tmp[3*Cout + T].  row_block0 / col_block0 / iter_block0: exclusive prefix sums of
  * Cout, of ceil(K/64) and of ceil(Cout/32) over the descriptors; the totals are passed alongside.  max_cout: largest Cout (sizes
@@ -347,10 +342,14 @@ int dgmr_bn_bwd_reduce(const float* gy, const float* x, const float* mean, const
 int dgmr_bn_bwd_apply(const float* gy, const float* x, const float* mean, const float* rstd, const float* gamma,
                       const double* sums, const float* dx_add, float* dx, float* dgamma, float* dbeta, int G, int64_t R,
                       int C, int train, void* stream);
-/* out[c] (+)= sum_r x[r][c]  (conv / linear bias gradient).  tmp: 2*C doubles of scratch (deterministic mode:
- * dgmr_reduce_doubles(1, R, C)), cleared by the call itself; not touched at all when R <= 4096 && C >= 4096 && C % 4 == 0
- * (few rows, many columns: one thread per column quad) - any non-NULL pointer will do there. */
+/* out[c] (+)= sum_r x[r][c]  (conv / linear bias gradient).  tmp: dgmr_colsum_tmp_doubles(R, C) doubles of scratch, cleared by the
+ * call itself. */
 int dgmr_colsum(const float* x, float* out, double* tmp, int64_t R, int C, int accumulate, void* stream);
+/* The doubles dgmr_colsum(.., R, C, ..) needs behind `tmp`, in the mode that is set when both are called.  Few rows x many columns
+ * (R <= 4096 && C >= 4096 && C % 4 == 0) go through a column-parallel kernel, one thread per column quad, that never touches tmp:
+ * 2 there (any non-NULL pointer will do).  Otherwise dgmr_reduce_doubles(1, R, C): 2*C, or the deterministic mode's rows.  Both
+ * functions decide the path by the same predicate, so a caller that sizes tmp from here never repeats the condition. */
+int64_t dgmr_colsum_tmp_doubles(int64_t R, int C);
 /* y = x*a[g][c]+b[g][c]  (BatchNorm1d apply; no relu) */
 int dgmr_affine(const float* x, const float* a, const float* b, float* y, int G, int64_t R, int C, int relu, void* stream);
 

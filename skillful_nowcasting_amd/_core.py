@@ -88,10 +88,10 @@ def sums_buffer(groups: int, rows: int, c: int, device, row_blocks: bool = True,
 
 
 def colsum_tmp(rows: int, c: int, device) -> torch.Tensor:
-    """`tmp` of dgmr_colsum over [rows][c].  Few rows x many columns go through a column-parallel kernel that never touches tmp (ops.hip:
-    R <= 4096, C >= 4096, C % 4 == 0 - the backward of a batch repeat / a group sum): two doubles stand in there instead of the
-    deterministic mode's per-workgroup rows (tens of MB per call)."""
-    if rows <= 4096 and c >= 4096 and c % 4 == 0:
+    """`tmp` of dgmr_colsum over [rows][c], sized by the library (dgmr_colsum_tmp_doubles, batchnorm.hip).  Few rows x many columns - the
+    backward of a batch repeat / a group sum - go through a column-parallel kernel that never touches tmp: two doubles stand in there
+    instead of the deterministic mode's per-workgroup rows (tens of MB per call)."""
+    if int(load().dgmr_colsum_tmp_doubles(rows, c)) == 2:  # (also the reduce path's own size for a single column, mode off)
         return torch.empty(2, device=device, dtype=torch.float64)
     return sums_buffer(1, rows, c, device, zero=False)
 

@@ -106,7 +106,6 @@ SIGNATURES = {
     "dgmr_wgrad_reduce_slice": [P, i, i, i, i, i, i, i, P, P, P, P, P],
     "dgmr_sn_wgrad_finalize": [P, P, P, P, P, P, i, i, i, i, i, P],
     "dgmr_spectral_sigma": [P, P, P, P, P, P, P, P, i, i, i, f, i, P],
-    "dgmr_spectral_sigma_seq": [P, P, P, P, P, P, P, P, P, i, i, i, f, i, P],
     "dgmr_spectral_sigma_seq_multi": [P, i, i, i, i, i, i, P, P],
     "dgmr_bn_stats": [P, P, i, L, i, P],
     "dgmr_bn_finalize": [P, P, P, P, P, P, P, P, P, P, i, L, i, f, f, P, P],
@@ -191,7 +190,8 @@ SIGNATURES = {
 }
 del i, f, L
 # buffer sizes: these return int64_t
-SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_grid_cell_acc_doubles": [c_int64],
+SIGNATURES_I64 = {"dgmr_reduce_doubles": [c_int, c_int64, c_int], "dgmr_colsum_tmp_doubles": [c_int64, c_int],
+                  "dgmr_grid_cell_acc_doubles": [c_int64],
                   "dgmr_ensemble_scores_workspace": [c_int, c_int64, c_int, c_int],
                   "dgmr_radial_psd_workspace": [c_int64, c_int, c_int, c_int],
                   "dgmr_probability_match_workspace": [c_int, c_int, c_int]}

@@ -12,7 +12,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void dgmr_set_error(const char* fmt, ...);
-extern int g_deterministic;  // dgmr_set_deterministic (ops.hip): fixed-order cross-workgroup sums
+// bn_param_grad_kernel (batchnorm.hip), also behind the sampler's output head (head.hip): dgamma / dbeta += the groups' backward sums
+void launch_bn_param_grad(const double* sums, float* dgamma, float* dbeta, int G, int C, hipStream_t s);
+extern int g_deterministic;  // dgmr_set_deterministic (lib.hip): fixed-order cross-workgroup sums
 
 #define DGMR_CHECK_ARG(cond, ...)        \
     do {                                 \
@@ -32,8 +34,9 @@ extern int g_deterministic;  // dgmr_set_deterministic (ops.hip): fixed-order cr
     } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-// Element-wise launches (ops.hip, optim.hip): 256 threads, a capped grid that strides over the items; `stream` is the entry point's argument.
+// Element-wise launches (elementwise.hip, optim.hip and the other HBM-bound units): 256 threads, a capped grid that strides over the items; `stream` is the entry point's argument.
 constexpr int EW_THREADS = 256;
 static inline int ew_blocks(int64_t n_items) { return (int)std::min<int64_t>((n_items + EW_THREADS - 1) / EW_THREADS, 256 * 16); }
 #define GRID_STRIDE(i, n) \

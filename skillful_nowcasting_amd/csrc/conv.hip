@@ -872,7 +872,6 @@ extern "C" int dgmr_conv_pool2_supported(const dgmr_conv_args* a) {
     return pooled_plan(p, &w) ? 1 : 0;
 }
 
-static inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 // DGMR_STEM4=0: A/B switch for the four-channel first-conv kernel
 static const bool g_stem4 = []() {
     const char* e = getenv("DGMR_STEM4");

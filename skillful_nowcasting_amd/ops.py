@@ -135,23 +135,6 @@ def weight_gram(w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     return a
 
 
-def spectral_sigma_seq(w: torch.Tensor, gram: torch.Tensor, u: torch.Tensor, v: torch.Tensor, scratch: torch.Tensor, eps: float,
-                       calls: int) -> SNCall:
-    """`calls` consecutive train-mode calls of one module (one power iteration each) in one go; see dgmr_spectral_sigma_seq."""
-    require_hip(w, "spectral-norm weight")
-    cout, cin = w.shape[0], w.shape[1]
-    taps = w.numel() // (cout * cin)
-    k = cin * taps
-    dev = w.device
-    inv_sigma = torch.empty(calls, device=dev, dtype=torch.float32)
-    u_hist = torch.empty(calls, cout, device=dev, dtype=torch.float32)
-    v_hist = torch.empty(calls, k, device=dev, dtype=torch.float32)
-    tmp = torch.empty(cout + calls, device=dev, dtype=torch.float32)
-    call("dgmr_spectral_sigma_seq", _p(w), _p(gram), _p(u), _p(v), _p(u_hist), _p(v_hist), _p(inv_sigma), _p(scratch), _p(tmp),
-         cout, cin, taps, float(eps), calls, _stream())
-    return SNCall(inv_sigma, u_hist, v_hist, calls)
-
-
 # ---------------------------------------------------------------------------------------------------
 # convolution
 # ---------------------------------------------------------------------------------------------------

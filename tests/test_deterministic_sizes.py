@@ -39,6 +39,21 @@ def test_scratch_sizes_follow_the_mode(lib):
     assert lib.dgmr_grid_cell_acc_doubles(100) == 2
 
 
+@pytest.mark.parametrize("det", [0, 1])
+@pytest.mark.parametrize("c", [4, 4092, 4096, 4098, 4100])
+@pytest.mark.parametrize("r", [1, 4096, 4097])
+def test_colsum_tmp_follows_the_dispatch(lib, r, c, det):
+    """dgmr_colsum_tmp_doubles: 2 exactly where dgmr_colsum takes its column-parallel path (the condition is restated here, not read
+    from the library), the reduction's own size everywhere else, in either mode."""
+    lib.dgmr_set_deterministic(det)
+    got = lib.dgmr_colsum_tmp_doubles(r, c)
+    if r <= 4096 and c >= 4096 and c % 4 == 0:
+        assert got == 2
+    else:
+        assert got == lib.dgmr_reduce_doubles(1, r, c)
+        assert got >= 2 * c
+
+
 @pytest.mark.parametrize("geom", [(1728, 1, 64, 64, 96, 96, 1, 3, 3, 0, 108), (288, 1, 128, 128, 96, 48, 1, 3, 3, 1, 18), (32, 22, 64, 64, 48, 48, 3, 3, 3, 0, 1),
                                   (96, 1, 8, 8, 384, 384, 1, 3, 3, 0, 6), (1728, 1, 64, 64, 48, 96, 1, 1, 1, 0, 108)])
 @pytest.mark.parametrize("precision", [0, 1, 2, 3])

@@ -324,3 +324,59 @@ def test_sampler_head_vs_torch(n, hw, c, groups):
     _close(bd.grad, br.grad, "bias gradient", 2e-5)
     _close(gd.grad, gr.grad, "gamma gradient", 2e-5)
     _close(bed.grad, ber.grad, "beta gradient", 2e-5)
+
+
+# ---- dgmr_colsum through the buffer _core.colsum_tmp sizes for it, on both sides of its dispatch ---------------------------------
+# (4096, 4096): the column-parallel kernel (tmp is two doubles); (4097, 4096): one row more, the double-accumulating reduction;
+# (64, 4098): columns that are no multiple of four, the reduction again.
+COLSUM_SHAPES = [(4096, 4096), (4097, 4096), (64, 4098)]
+
+
+@pytest.fixture(scope="module")
+def colsum_data():
+    """One fp32 matrix per column count (the 4096-row case is the first rows of the 4097-row one), its float64 column sums and the
+    column sums of |x|; computed once, never written."""
+    torch.manual_seed(11)
+    mats = {4096: torch.randn(4097, 4096, device=DEV), 4098: torch.randn(64, 4098, device=DEV)}
+    out0 = {c: torch.randn(c, device=DEV) for c in mats}
+    data = {}
+    for r, c in COLSUM_SHAPES:
+        x = mats[c][:r]
+        data[(r, c)] = (x, x.double().sum(0), x.double().abs().sum(0), out0[c])
+    return data
+
+
+@pytest.mark.parametrize("det", [False, True])
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("r,c", COLSUM_SHAPES)
+def test_colsum_through_colsum_tmp(colsum_data, r, c, accumulate, det):
+    """out[c] (+)= sum_r x[r][c] against torch.sum in float64 of the same fp32 data.  The bound is the arithmetic's, not a run's: a
+    sum of terms formed with at most R fp32 additions in any order is off by at most gamma_R * sum |terms|,
+    gamma_R = R 2^-24 / (1 - R 2^-24) (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2); the terms are the R rows
+    and, with accumulate, the value `out` held before.  The reduction accumulates in double and rounds once or twice: far inside."""
+    import skillful_nowcasting_amd as S
+    from skillful_nowcasting_amd._core import _p, _stream, colsum_tmp
+    from skillful_nowcasting_amd._lib import call
+
+    x, ref, ref_abs, out0 = colsum_data[(r, c)]
+    was = S.deterministic()
+    S.set_deterministic(det)
+    try:
+        outs = []
+        for _ in range(2):
+            out = out0.clone() if accumulate else torch.full((c,), float("nan"), device=DEV)
+            tmp = colsum_tmp(r, c, x.device)
+            call("dgmr_colsum", _p(x), _p(out), _p(tmp), r, c, accumulate, _stream())
+            outs.append(out)
+        torch.cuda.synchronize()
+    finally:
+        S.set_deterministic(was)
+    want = ref + out0.double() if accumulate else ref
+    terms = ref_abs + out0.double().abs() if accumulate else ref_abs
+    u = r * 2.0 ** -24
+    bound = u / (1.0 - u) * terms
+    err = (outs[0].double() - want).abs()
+    ratio = (err / bound).max().item()
+    assert bool((err <= bound).all()), f"colsum {r} x {c} accumulate={accumulate} det={det}: worst error / bound = {ratio:.3e}"
+    if det:
+        assert torch.equal(outs[0], outs[1]), "deterministic mode: two calls differ"

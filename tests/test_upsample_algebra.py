@@ -1,6 +1,6 @@
 """The three decompositions of the upsampling conv (UpsampleGBlock.first_conv_3x3: nearest-2x, then 3x3; dgmr/common.py:142,148) that the
 HIP path executes instead of the conv as written, restated in float64 on the CPU with the index formulas of the kernels
-(csrc/conv.hip: phase_weights_kernel, pool2_weights_kernel; csrc/ops.hip: upsample_wgrad_sums_kernel) and checked against torch's own
+(csrc/conv.hip: phase_weights_kernel, pool2_weights_kernel; csrc/layout.hip: upsample_wgrad_sums_kernel) and checked against torch's own
 conv / autograd.  Round 4 adds the weight gradient by output-pixel parity (csrc/wgrad_ws.h PHASE) and the DBlock tail - conv + AvgPool as one
 pooled pass, 3-D plane by plane, shortcut conv on the pooled map (common.DBlock, ops.ConvFn._forward_pooled).  No GPU: this pins the algebra;
 tests/test_gpu_kernels.py and tests/test_gpu_precision.py pin the kernels."""
