@@ -53,6 +53,10 @@ class SNPlan:
             cout, cin = w.shape[0], w.shape[1]
             taps = w.numel() // (cout * cin)
             k = cin * taps
+            if cin % 4:
+                # sn_rows_multi_kernel reads W in float4 steps that must not straddle a tap (dgmr_spectral_sigma checks the same)
+                raise RuntimeError(f"skillful_nowcasting_amd: spectral-norm plan: module {i} ({type(m).__name__}) has Cin={cin}; the "
+                                   "power-iteration kernels need Cin to be a multiple of 4")
             gram = m._gram_buffer()
             d = descs[i]
             d.w, d.gram, d.u, d.v = w.data_ptr(), gram.data_ptr(), vec._u.data_ptr(), vec._v.data_ptr()

@@ -51,6 +51,21 @@ def test_plan_layout_is_disjoint_and_complete():
     assert plan.max_cout == 16
 
 
+def test_plan_refuses_cin_not_a_multiple_of_4():
+    """sn_rows_multi_kernel reads K in float4 steps that must not straddle a tap: the plan refuses such a module where it is built,
+    as the single-call entry point does, and names it; the modules beside it are fine on their own."""
+    import pytest
+
+    from skillful_nowcasting_amd.nn import SNConv, SNLinear1, SNPlan
+
+    torch.manual_seed(0)
+    ok = SNConv(8, 16, 3)
+    for bad in (SNConv(6, 16, 3), SNConv(1, 8, 1), SNLinear1(30)):
+        with pytest.raises(RuntimeError, match=r"module 1 .*Cin=\d+.*multiple of 4"):
+            SNPlan([(ok, 2, None), (bad, 3, None)])
+    assert SNPlan([(ok, 2, None)]).max_calls == 2
+
+
 def test_plan_valid_tracks_pointers():
     from skillful_nowcasting_amd.nn import SNPlan
 
