@@ -856,7 +856,9 @@ int dgmr_conv_tune(int variant, int ksplit, int window, int wgrad_window);
  * partial sums from its epilogue (stats_out) and dgmr_conv_stats_rows answers for it (DGMR_CONV1X1_STATS=1 for a whole process; off by
  * default); 1024 = dgmr_wgrad_reduce[_slice] never take their two-stage path (DGMR_WGRAD_NARROW=0; same bits either way); 2048 =
  * dgmr_sn_wgrad_finalize uses its one-thread-per-element kernel (DGMR_SN_FINALIZE_TILED=0; same bits either way); 4096 = dispatch probe:
- * the LDS-tiled finalize kernel, where dgmr_sn_wgrad_finalize launches it, returns at once and gw keeps its values (garbage by design). */
+ * the LDS-tiled finalize kernel, where dgmr_sn_wgrad_finalize launches it, returns at once and gw keeps its values (garbage by design).
+ * 8192 = BatchNorm's stream passes (dgmr_bn_stats / _bwd_reduce / _bwd_apply, dgmr_colsum and the two serial walks behind them) keep
+ * one row in flight per lane on their former grids instead of several (same bits either way; the tests' reference and the A/B). */
 int dgmr_debug_flags(int flags);
 
 #ifdef __cplusplus

@@ -1,5 +1,7 @@
 // Per-channel reductions over [G][R][C] and BatchNorm for gfx950: statistics, finalize, backward, column / row sums, repeats and the
 // affine apply.  HBM-bound; the reductions accumulate in double so that E[x^2] - E[x]^2 stays accurate.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -7,13 +9,17 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // per-channel reductions over [G][R][C]
 // ------------------------------------------------------------------------------------------------
-// F: void(int64_t elem_index, int g, int c, double& s0, double& s1)
+// K: coef(int g, int c) -> the thread's loop-invariant coefficients; L: load(int64_t elem_index) -> the element's operands;
+// A: acc(operands, coefficients, double& s0, double& s1).  A thread owns one (channel, row lane) and adds its rows in ascending order
+// onto one chain; UNR is only how many rows' loads it issues before the additions of the first of them (1: a load, a wait and an
+// addition per row - one 4-byte load in flight per lane, 2.8 TB/s with the chip to itself).
 // Accumulation is in double from the first element on.  Batch variance is formed as E[x^2] - mean^2, which cancels by mean^2 / var:
 // the discriminator heads normalise relu-sum features whose spread across the 8 ... 32 samples of a call is ~1 % of their mean
 // (mean^2 / var ~ 1e4), and float partial sums (6e-8 x 1e4 = 6e-4 on rstd) put a 1e-3 ... 1e-2 error on every gradient behind the
 // head (found by tests/test_gpu_stages.py::test_temporal_discriminator_backward_stages).  These kernels are HBM-bound either way.
-template <class F>
-__device__ __forceinline__ void chan_reduce2(F f, int64_t R, int C, double* __restrict__ out /* [G][2][C] */, int det = 0) {
+constexpr int RED_UNR = 8;  // rows in flight per lane in the reductions and the two serial walks (dgmr_debug_flags 8192: 1)
+template <int UNR, class K, class L, class A>
+__device__ __forceinline__ void chan_reduce2(K coef, L load, A acc, int64_t R, int C, double* __restrict__ out /* [G][2][C] */, int det = 0) {
     __shared__ double l0[256], l1[256];
     const int g = blockIdx.y;
     const int64_t rows_per_block = (R + gridDim.x - 1) / gridDim.x;
@@ -23,8 +29,31 @@ __device__ __forceinline__ void chan_reduce2(F f, int64_t R, int C, double* __re
         const int RL = 256 / Wd;
         const int c = cb + threadIdx.x % Wd, rl = threadIdx.x / Wd;
         double s0 = 0.0, s1 = 0.0;
-        if (rl < RL)
-            for (int64_t r = r0 + rl; r < r1; r += RL) f(((int64_t)g * R + r) * C + c, g, c, s0, s1);
+        if (rl < RL) {
+            const auto k = coef(g, c);
+            const int64_t e0 = (int64_t)g * R * C + c, step = (int64_t)RL * C;  // element of row r: e0 + r * C
+            int64_t r = r0 + rl;
+            if constexpr (UNR > 1) {
+                for (; r + (int64_t)(UNR - 1) * RL < r1; r += (int64_t)UNR * RL) {
+                    decltype(load(e0)) v[UNR];
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) v[u] = load(e0 + r * C + u * step);
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) acc(v[u], k, s0, s1);
+                }
+                if (r < r1) {  // the last, short batch: only rows below r1 are read
+                    decltype(load(e0)) v[UNR - 1];
+#pragma unroll
+                    for (int u = 0; u < UNR - 1; ++u)
+                        if (r + (int64_t)u * RL < r1) v[u] = load(e0 + r * C + u * step);
+#pragma unroll
+                    for (int u = 0; u < UNR - 1; ++u)
+                        if (r + (int64_t)u * RL < r1) acc(v[u], k, s0, s1);
+                }
+            } else {
+                for (; r < r1; r += RL) acc(load(e0 + r * C), k, s0, s1);
+            }
+        }
         l0[threadIdx.x] = s0;
         l1[threadIdx.x] = s1;
         __syncthreads();
@@ -47,23 +76,37 @@ __device__ __forceinline__ void chan_reduce2(F f, int64_t R, int C, double* __re
     }
 }
 
-// out[j] += sum over rows b = 0 .. nb-1 of out[(1 + b) * n + j], in that order (deterministic mode of the per-channel reductions)
+// out[j] += sum over rows b = 0 .. nb-1 of out[(1 + b) * n + j], in that order (deterministic mode of the per-channel reductions);
+// UNR rows are loaded ahead of their additions
+template <int UNR>
 __global__ void reduce_rows_finish_kernel(double* __restrict__ out, int nb, int64_t n) {
     GRID_STRIDE(j, n) {
         double a = 0.0;
-        for (int b = 0; b < nb; ++b) a += out[(size_t)(1 + b) * n + j];
+        int b = 0;
+        if constexpr (UNR > 1)
+            for (; b + UNR <= nb; b += UNR) {
+                double v[UNR];
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) v[u] = out[(size_t)(1 + b + u) * n + j];
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) a += v[u];
+            }
+        for (; b < nb; ++b) a += out[(size_t)(1 + b) * n + j];
         out[j] += a;
     }
 }
 
+struct NoCoef {};
+
+template <int UNR>
 __global__ void bn_stats_kernel(const float* __restrict__ x, double* __restrict__ sums, int64_t R, int C, int det) {
-    chan_reduce2(
-        [&](int64_t i, int, int, double& s0, double& s1) {
-            const double v = (double)x[i];
-            s0 += v;
-            s1 = fma(v, v, s1);
-        },
-        R, C, sums, det);
+    chan_reduce2<UNR>([](int, int) { return NoCoef{}; }, [&](int64_t i) { return x[i]; },
+                      [](float xv, NoCoef, double& s0, double& s1) {
+                          const double v = (double)xv;
+                          s0 += v;
+                          s1 = fma(v, v, s1);
+                      },
+                      R, C, sums, det);
 }
 
 // deterministic bn_partial_reduce: one workgroup per (32 columns, group); 8 row lanes sum rows r = lane (mod 8) in order, then in lane order
@@ -105,20 +148,31 @@ __global__ void bn_bwd_center_kernel(double* __restrict__ sums, const float* __r
     }
 }
 
+struct GX {
+    float g, x;
+};
+struct MeanRstd {
+    float mean, rstd;
+};
+
+template <int UNR>
 __global__ void bn_bwd_reduce_kernel(const float* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ mean,
                                      const float* __restrict__ rstd, double* __restrict__ sums, int64_t R, int C, int det) {
-    chan_reduce2(
-        [&](int64_t i, int g, int c, double& s0, double& s1) {
-            const float gv = gy[i];
-            const float xh = (x[i] - mean[(size_t)g * C + c]) * rstd[(size_t)g * C + c];
-            s0 += (double)gv;
-            s1 = fma((double)gv, (double)xh, s1);
-        },
-        R, C, sums, det);
+    chan_reduce2<UNR>([&](int g, int c) { return MeanRstd{mean[(size_t)g * C + c], rstd[(size_t)g * C + c]}; },
+                      [&](int64_t i) { return GX{gy[i], x[i]}; },
+                      [](GX v, MeanRstd k, double& s0, double& s1) {
+                          const float gv = v.g;
+                          const float xh = (v.x - k.mean) * k.rstd;
+                          s0 += (double)gv;
+                          s1 = fma((double)gv, (double)xh, s1);
+                      },
+                      R, C, sums, det);
 }
 
+template <int UNR>
 __global__ void colsum_kernel(const float* __restrict__ x, double* __restrict__ sums, int64_t R, int C, int det) {
-    chan_reduce2([&](int64_t i, int, int, double& s0, double&) { s0 += (double)x[i]; }, R, C, sums, det);
+    chan_reduce2<UNR>([](int, int) { return NoCoef{}; }, [&](int64_t i) { return x[i]; },
+                      [](float xv, NoCoef, double& s0, double&) { s0 += (double)xv; }, R, C, sums, det);
 }
 
 // out[c] (+)= sum_r x[r][c] for FEW rows and MANY columns (one thread per 4 columns; colsum_kernel is for the opposite shape)
@@ -262,52 +316,127 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ gy, const float* _
     }
 }
 
+// One float4 of the 16-byte kernel.  The scalar kernel's expression per element, v - k0 * invR - xh * k1 * invR, then * gr, then + dx_add,
+// written out in the one contracted form the compiler had chosen for the former loop - v - rn(k0 * invR) first, then one fma of
+// -invR and rn(xh * k1) onto it - with contraction off around it: left to the compiler, the instantiations and their predicated
+// last passes came out in different forms (fma(-k0, invR, v) in some), a last-bit difference in 6 % of the elements.
+typedef __attribute__((address_space(1))) f32x4 gf32x4;  // a float4 in global memory (a pointer rebuilt from two scalars keeps its space)
+template <bool TRAIN>
+__device__ __forceinline__ f32x4 bn_bwd_apply_quad(f32x4 v, const f32x4 xv, const f32x4 mn, const f32x4 rs, const f32x4 k0, const f32x4 k1,
+                                                   const f32x4 gr, const float invR, const bool has_add, const gf32x4* add) {
+#pragma clang fp contract(off)
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float xh = (xv[j] - mn[j]) * rs[j];
+            v[j] = __builtin_fmaf(-invR, xh * k1[j], v[j] - k0[j] * invR);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] *= gr[j];
+    if (has_add) v += __builtin_nontemporal_load(add);
+    return v;
+}
+
 // The same, 16 bytes per lane: the grid stride is a multiple of C / 4, so a thread's channel quad - and its five coefficient quads -
 // never change over its rows (the scalar kernel spends a 64-bit modulo and seven dependent loads per element: 4.3 TB/s of HBM
-// traffic where a streaming kernel reaches ~6).  Same expression per element as above.
+// traffic where a streaming kernel reaches ~6).  A lane keeps U rows in flight: per pass it issues the U float4 of gy and of x back to
+// back (rows at or past n4 are not loaded), uses them in row order and stores U results; the first pass's loads are issued before
+// the ~20 coefficient loads, so that round trip runs under the stream and not in front of it.  U = 1 on the former grid (two rows
+// per lane, a workgroup of three serial round trips) is dgmr_debug_flags 8192: the tests' reference, and the A/B.  U = 2 is the
+// default (61 VGPRs: eight waves per SIMD, resident beside a weight-gradient workgroup; DESIGN.md 7d: the step prefers it to 4 and 8).
+template <int U, bool TRAIN>
 __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const f32x4* __restrict__ gy, const f32x4* __restrict__ x,
                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
                                                              const float* __restrict__ gamma, const double* __restrict__ sums,
                                                              const f32x4* __restrict__ dx_add, f32x4* __restrict__ dx,
-                                                             int64_t n4, int C, float invR, int train) {
+                                                             int64_t n4, int C, float invR) {
     const int g = blockIdx.y;
     const int C4 = C >> 2;
-    const int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    // a pass covers U * stride float4 from the uniform index p on; inside it a lane's rows sit at i0 + u * stride < 8 * 2^24 (the host
+    // keeps gridDim.x <= 65536), so their byte offsets fit 32 bits and serve gy, x, dx_add and dx alike on a uniform 64-bit base
+    const uint32_t i0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+    const size_t base = (size_t)g * n4;
+    // (the pass's base goes through readfirstlane: it stays one scalar pair per operand, with the lane's 32-bit offset beside it, where
+    //  the loop optimiser otherwise keeps a 64-bit vector pointer per operand and row - 32 more registers at U = 4)
+    const auto at = [](const f32x4* q, uint32_t bytes) {
+        const uint64_t v = (uint64_t)q;
+        // (the builtin returns int: both halves go through uint32_t, or a low half >= 2^31 sign-extends over the high one)
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+        return (gf32x4*)((((uint64_t)hi << 32) | lo) + bytes);
+    };
+    const bool has_add = dx_add != nullptr;
+    const int64_t pass = (int64_t)U * stride;
     const int c = (int)(i0 % C4) * 4;
     f32x4 mn, rs, k0, k1, gr;
+    // one pass from the uniform index p on.  FULL: every row of it lies below n4 for every lane (a uniform condition) - no predicates;
+    // FIRST: the coefficient loads go between the pass's loads and their first use.  The rows live inside the pass: nothing is
+    // carried from one to the next.
+    const auto run = [&](int64_t p, auto full, auto first) {
+        const uint32_t rem = (uint32_t)min(n4 - p, (int64_t)1 << 28);
+        f32x4 gv[U], xv[U];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const size_t gc = (size_t)g * C + c + j;
-        mn[j] = mean[gc];
-        rs[j] = rstd[gc];
-        k0[j] = (float)sums[((size_t)g * 2 + 0) * C + c + j];
-        k1[j] = (float)sums[((size_t)g * 2 + 1) * C + c + j];
-        gr[j] = (gamma ? gamma[c + j] : 1.f) * rs[j];
-    }
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const size_t base = (size_t)g * n4;
-    for (int64_t i = i0; i < n4; i += stride) {
-        f32x4 v = __builtin_nontemporal_load(gy + base + i);
-        if (train) {
-            const f32x4 xv = __builtin_nontemporal_load(x + base + i);
+        for (int u = 0; u < U; ++u)
+            if (decltype(full)::value || i0 + u * stride < rem) {
+                gv[u] = __builtin_nontemporal_load(at(gy + base + p, (i0 + u * stride) * 16u));
+                if constexpr (TRAIN) xv[u] = __builtin_nontemporal_load(at(x + base + p, (i0 + u * stride) * 16u));
+            }
+        if constexpr (decltype(first)::value) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float xh = (xv[j] - mn[j]) * rs[j];
-                v[j] = v[j] - k0[j] * invR - xh * k1[j] * invR;
+                const size_t gc = (size_t)g * C + c + j;
+                rs[j] = rstd[gc];
+                if constexpr (TRAIN) {
+                    mn[j] = mean[gc];
+                    k0[j] = (float)sums[((size_t)g * 2 + 0) * C + c + j];
+                    k1[j] = (float)sums[((size_t)g * 2 + 1) * C + c + j];
+                }
+                gr[j] = (gamma ? gamma[c + j] : 1.f) * rs[j];
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= gr[j];
-        if (dx_add) v += __builtin_nontemporal_load(dx_add + base + i);
-        dx[base + i] = v;
+        for (int u = 0; u < U; ++u)
+            if (decltype(full)::value || i0 + u * stride < rem) {
+                const uint32_t bytes = (i0 + u * stride) * 16u;
+                *at(dx + base + p, bytes) =
+                    bn_bwd_apply_quad<TRAIN>(gv[u], xv[u], mn, rs, k0, k1, gr, invR, has_add, at(dx_add + base + p, bytes));
+            }
+    };
+    const std::true_type yes;
+    const std::false_type no;
+    if (pass > n4) {  // less than one pass in all
+        run(0, no, yes);
+        return;
     }
+    run(0, yes, yes);
+    int64_t p = pass;
+    for (; p + pass <= n4; p += pass) run(p, yes, no);
+    if (p < n4) run(p, no, no);  // the ragged last pass
 }
 
+// one thread per channel walks the G groups in order; UNR groups' 2 UNR doubles are loaded ahead of their additions
+template <int UNR>
 __global__ void bn_param_grad_kernel(const double* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta, int G,
                                      int C) {
     GRID_STRIDE(c, C) {
         double s0 = 0.0, s1 = 0.0;
-        for (int g = 0; g < G; ++g) {
+        int g = 0;
+        if constexpr (UNR > 1)
+            for (; g + UNR <= G; g += UNR) {
+                double v0[UNR], v1[UNR];
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+                    v0[u] = sums[((size_t)(g + u) * 2 + 0) * C + c];
+                    v1[u] = sums[((size_t)(g + u) * 2 + 1) * C + c];
+                }
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+                    s0 += v0[u];
+                    s1 += v1[u];
+                }
+            }
+        for (; g < G; ++g) {
             s0 += sums[((size_t)g * 2 + 0) * C + c];
             s1 += sums[((size_t)g * 2 + 1) * C + c];
         }
@@ -331,8 +460,26 @@ __global__ void affine_kernel(const float* __restrict__ x, const float* __restri
 }  // namespace
 
 // bn_param_grad_kernel for the units that hold BatchNorm backward sums of their own (head.hip); launch errors are the caller's to check
+// dgmr_debug_flags 8192 (conv.hip sets it): the stream passes as they were - one row in flight per lane on the former grids (the
+// tests' reference and the A/B; the same bits either way)
+int g_bn_one_row = 0;
+static inline bool one_row_in_flight() { return g_bn_one_row != 0; }
+#define LAUNCH_UNR(kernel, grid, block, s, ...)                                             \
+    do {                                                                                    \
+        if (one_row_in_flight()) hipLaunchKernelGGL(kernel<1>, grid, block, 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<RED_UNR>, grid, block, 0, s, __VA_ARGS__);            \
+    } while (0)
+
+// DGMR_BN_ROWS = 2 / 4 / 8: rows a lane of bn_bwd_apply4_kernel keeps in flight (A/B; the same bits for every value)
+static const int g_bn_rows = []() {
+    const char* e = getenv("DGMR_BN_ROWS");
+    const int u = e ? atoi(e) : 0;
+    return (u == 2 || u == 4 || u == 8) ? u : 2;
+}();
+constexpr int BN_APPLY_WGS = 256 * 8;  // workgroups per launch of the multi-pass grid: 8 per CU
+
 void launch_bn_param_grad(const double* sums, float* dgamma, float* dbeta, int G, int C, hipStream_t s) {
-    hipLaunchKernelGGL(bn_param_grad_kernel, dim3((C + 255) / 256), dim3(256), 0, s, sums, dgamma, dbeta, G, C);
+    LAUNCH_UNR(bn_param_grad_kernel, dim3((C + 255) / 256), dim3(256), s, sums, dgamma, dbeta, G, C);
 }
 
 static inline dim3 reduce_grid(int G, int64_t R) {
@@ -359,12 +506,12 @@ static inline dim3 reduce_grid_mode(int G, int64_t R, int C) {
 static inline void reduce_finish(double* sums, int G, int64_t R, int C, hipStream_t s) {
     if (!g_deterministic) return;
     const int64_t n = (int64_t)G * 2 * C;
-    hipLaunchKernelGGL(reduce_rows_finish_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, s, sums, det_blocks(G, R, C), n);
+    LAUNCH_UNR(reduce_rows_finish_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), s, sums, det_blocks(G, R, C), n);
 }
 
 extern "C" int dgmr_bn_stats(const float* x, double* sums, int G, int64_t R, int C, void* stream) {
     DGMR_CHECK_ARG(x && sums && G > 0 && R > 0 && C > 0, "dgmr_bn_stats: bad args");
-    hipLaunchKernelGGL(bn_stats_kernel, reduce_grid_mode(G, R, C), dim3(256), 0, ST, x, sums, R, C, g_deterministic);
+    LAUNCH_UNR(bn_stats_kernel, reduce_grid_mode(G, R, C), dim3(256), ST, x, sums, R, C, g_deterministic);
     reduce_finish(sums, G, R, C, ST);
     DGMR_CHECK_LAUNCH();
     return 0;
@@ -405,7 +552,7 @@ extern "C" int dgmr_bn_finalize(const double* sums, const float* gamma, const fl
 extern "C" int dgmr_bn_bwd_reduce(const float* gy, const float* x, const float* mean, const float* rstd, double* sums, int G,
                                   int64_t R, int C, void* stream) {
     DGMR_CHECK_ARG(gy && x && mean && rstd && sums, "dgmr_bn_bwd_reduce: null pointer");
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, reduce_grid_mode(G, R, C), dim3(256), 0, ST, gy, x, mean, rstd, sums, R, C, g_deterministic);
+    LAUNCH_UNR(bn_bwd_reduce_kernel, reduce_grid_mode(G, R, C), dim3(256), ST, gy, x, mean, rstd, sums, R, C, g_deterministic);
     reduce_finish(sums, G, R, C, ST);
     DGMR_CHECK_LAUNCH();
     return 0;
@@ -417,15 +564,38 @@ extern "C" int dgmr_bn_bwd_apply(const float* gy, const float* x, const float* m
     DGMR_CHECK_ARG(gy && x && mean && rstd && sums && dx, "dgmr_bn_bwd_apply: null pointer");
     const int64_t n4 = R * C / 4;
     if (C % 4 == 0 && C / 4 <= 4096 && al16(gy) && al16(x) && al16(dx) && al16(dx_add)) {
-        // blocks: a multiple of m = (C/4) / gcd(C/4, 256) so that blocks * 256 is a multiple of C/4; ~2 float4 per thread per operand
+        // blocks: a multiple of m = (C/4) / gcd(C/4, 256) so that blocks * 256 is a multiple of C/4
         const int C4 = C / 4;
         int a = C4, b = 256;
         while (b) { const int t = a % b; a = b; b = t; }
         const int m = C4 / a;
-        int64_t blocks = (n4 + 2 * 256 - 1) / (2 * 256);
-        blocks = std::min<int64_t>(std::max<int64_t>((blocks + m - 1) / m * m, m), (int64_t)(65536 / m) * m);
-        hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3((unsigned)blocks, G), dim3(256), 0, ST, (const f32x4*)gy, (const f32x4*)x, mean, rstd,
-                           gamma, sums, (const f32x4*)dx_add, (f32x4*)dx, n4, C, 1.f / (float)R, train);
+        const int U = one_row_in_flight() ? 1 : g_bn_rows;
+        int64_t blocks;
+        if (U == 1) {  // the former launch: ~2 float4 per thread per operand
+            blocks = (n4 + 2 * 256 - 1) / (2 * 256);
+            blocks = std::min<int64_t>(std::max<int64_t>((blocks + m - 1) / m * m, m), (int64_t)(65536 / m) * m);
+        } else {  // one pass of U rows per lane where that covers the tensor, else BN_APPLY_WGS workgroups over grid.x * G and several passes
+            blocks = (n4 + (int64_t)U * 256 - 1) / ((int64_t)U * 256);
+            blocks = std::max<int64_t>((blocks + m - 1) / m * m, m);
+            blocks = std::min<int64_t>(blocks, std::max<int64_t>(BN_APPLY_WGS / G / m * m, m));
+        }
+        const dim3 grid((unsigned)blocks, G);
+#define BN_APPLY4(U_, T_)                                                                                                            \
+    hipLaunchKernelGGL((bn_bwd_apply4_kernel<U_, T_>), grid, dim3(256), 0, ST, (const f32x4*)gy, (const f32x4*)x, mean, rstd, gamma, \
+                       sums, (const f32x4*)dx_add, (f32x4*)dx, n4, C, 1.f / (float)R)
+#define BN_APPLY4_U(U_)            \
+    do {                           \
+        if (train) BN_APPLY4(U_, true); \
+        else BN_APPLY4(U_, false); \
+    } while (0)
+        switch (U) {
+            case 1: BN_APPLY4_U(1); break;
+            case 2: BN_APPLY4_U(2); break;
+            case 4: BN_APPLY4_U(4); break;
+            default: BN_APPLY4_U(8); break;
+        }
+#undef BN_APPLY4_U
+#undef BN_APPLY4
     } else {
         hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_blocks(R * C), G), dim3(EW_THREADS), 0, ST, gy, x, mean, rstd, gamma, sums,
                            dx_add, dx, R, C, train);
@@ -449,7 +619,7 @@ extern "C" int dgmr_colsum(const float* x, float* out, double* tmp, int64_t R, i
         return 0;
     }
     (void)hipMemsetAsync(tmp, 0, sizeof(double) * 2 * C, ST);  // (deterministic mode: tmp holds dgmr_reduce_doubles(1, R, C) doubles)
-    hipLaunchKernelGGL(colsum_kernel, reduce_grid_mode(1, R, C), dim3(256), 0, ST, x, tmp, R, C, g_deterministic);
+    LAUNCH_UNR(colsum_kernel, reduce_grid_mode(1, R, C), dim3(256), ST, x, tmp, R, C, g_deterministic);
     reduce_finish(tmp, 1, R, C, ST);
     hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, ST, tmp, out, C, accumulate);
     DGMR_CHECK_LAUNCH();

@@ -1559,12 +1559,15 @@ extern "C" int dgmr_conv_tune(int variant, int ksplit, int window, int wgrad_win
     return 0;
 }
 
+extern int g_bn_one_row;  // batchnorm.hip: bit 8192 of the flags
 extern "C" int dgmr_debug_flags(int flags) {
     // (256: phase launches one workgroup per ROW parity; 512: the 1x1 kernel's statistics ON; 1024 / 2048: the two-stage narrow reduce
     //  and the tiled finalize OFF, as by their environment switches - tests, A/B; 4096: the tiled finalize, where it is dispatched,
-    //  writes nothing - the tests' proof of which kernel ran)
-    DGMR_CHECK_ARG(flags >= 0 && flags <= 8191 && !(flags & 4), "dgmr_debug_flags: %d", flags);
+    //  writes nothing - the tests' proof of which kernel ran; 8192: BatchNorm's stream passes with one row in flight per lane, as
+    //  they were - batchnorm.hip)
+    DGMR_CHECK_ARG(flags >= 0 && flags <= 16383 && !(flags & 4), "dgmr_debug_flags: %d", flags);
     g_debug_flags = flags;
+    g_bn_one_row = (flags & 8192) != 0;
     return 0;
 }
 
