@@ -728,6 +728,22 @@ int dgmr_advect(const float* x, int64_t x_plane_stride, const float* field, int6
  * share their case's motion).  Every source value below 0 (or NaN) reads as 0.  Everything else - the D_t recursion, the arithmetic,
  * the store widths, the bound with A and max|x| taken over all steps' sources, the refusals - is dgmr_advect's;
  * x_step_stride = 0 with field_group = 1 gives dgmr_advect's bits.
+ *
+ * dgmr_advect_series_perturbed (a new symbol, same ABI version): dgmr_advect_series with a velocity error per plane and lead time, along and across the
+ * local motion (STEPS' perturbed motion vectors; stochastic.py).  direction[n / field_group][gy][gx][2] = (uy, ux): a second fp32
+ * lattice of the field's geometry (Gy, Gx, origin, spacing) and plane mapping, direction_plane_stride elements per plane (0: one for
+ * all planes), which the CALLER has normalised (advection.unit_directions: v / |v|, (0, 0) at calm nodes) - the kernel divides by
+ * nothing and takes no root.  amplitude[n][t - 1][2] = (a_par, a_perp) in pixels per step, contiguous, N T pairs.  At q = p - D_(t-1)(p),
+ * with u(q) the bilinear interpolation of the direction lattice through the field's node indices and weights:
+ *   vy' = fma(a_par, uy, fma(a_perp, -ux, vy)),  vx' = fma(a_par, ux, fma(a_perp, uy, vx))      (the perpendicular of u is (-ux, uy))
+ *   D_t(p) = D_(t-1)(p) + v'(q);  out[n][t - 1][p] = s_t(p - D_t(p)).
+ * a = 0 gives dgmr_advect_series' bits for finite directions.  Against exact arithmetic the result is within
+ *   c' T max(H, W) 2^-24 A + 4 * 2^-24 max|x|,  c' = 50:  per step and axis the 10 operations of dgmr_advect, 2 x 6 for the
+ * interpolations of the two direction components an axis of v' takes and 2 for its fmas, + 1 for the sample position, on two axes
+ * (advect.hip lists them) - for a TOTAL velocity v' that changes by less than 1 / (4 T) pixels per pixel and displacements that stay
+ * below max(H, W).  Layouts, store widths and refusals are dgmr_advect_series'; in addition direction and amplitude must not be null
+ * and direction_plane_stride has field_plane_stride's range.  Argument errors return < 0 and set dgmr_last_error() before anything
+ * is enqueued.  Runs on `stream`, does not synchronise.
  * ---------------------------------------------------------------------------------------------- */
 int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const float* white, int64_t white_member_stride, int64_t white_step_stride,
                      const float* rho, int P, int M, int T, int H, int W, int L, float* out, int64_t out_member_stride,
@@ -735,6 +751,10 @@ int dgmr_spectral_ar(const float* z0, int64_t z0_plane_stride, const float* whit
 int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_t x_step_stride, const float* field, int64_t field_plane_stride,
                        int field_group, int64_t N, int H, int W, int Gy, int Gx, float origin, float spacing, int T, float* out,
                        int64_t out_plane_stride, int64_t out_step_stride, void* stream);
+int dgmr_advect_series_perturbed(const float* x, int64_t x_plane_stride, int64_t x_step_stride, const float* field,
+                                 int64_t field_plane_stride, const float* direction, int64_t direction_plane_stride, const float* amplitude,
+                                 int field_group, int64_t N, int H, int W, int Gy, int Gx, float origin, float spacing, int T, float* out,
+                                 int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Lag spectra: the radially binned cross-spectrum of two planes over the windows and bins dgmr_spectral_ar evolves (stochastic.py:

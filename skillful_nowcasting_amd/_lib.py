@@ -161,6 +161,7 @@ SIGNATURES = {
     "dgmr_spectral_ar": [P, L, P, L, L, P, i, i, i, i, i, i, P, L, L, P],
     "dgmr_spectral_ar2": [P, L, P, L, P, L, L, P, L, i, i, i, i, i, i, P, L, L, P],
     "dgmr_advect_series": [P, L, L, P, L, i, L, i, i, i, i, f, f, i, P, L, L, P],
+    "dgmr_advect_series_perturbed": [P, L, L, P, L, P, L, P, i, L, i, i, i, i, f, f, i, P, L, L, P],
     "dgmr_lag_spectra": [P, L, P, L, L, i, i, i, P, P],
     "dgmr_probability_match": [P, L, L, P, L, P, L, L, i, i, i, i, i, f, f, P, L, P, L, L, P],
     "dgmr_upsample_phase_weights": [P, P, i, i, P],

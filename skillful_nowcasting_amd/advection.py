@@ -8,6 +8,8 @@ paper plots DGMR against; INTEGRATION.md "A baseline to beat").
   * `advect`: the last frame extrapolated along the field for all lead times, each lead time interpolating the source once;
   * `advect_series`: the same with a source of its own per lead time and one field per group of planes (`dgmr_advect_series`) -
     what `stochastic.EnsembleAdvectionNowcaster` moves its members with;
+  * `advect_series_perturbed`: `advect_series` with a velocity error per plane and lead time along and across the directions of
+    `unit_directions` (`dgmr_advect_series_perturbed`) - the members' perturbed motion vectors;
   * `AdvectionNowcaster`, `persistence_nowcast`: forecasts in the layout of `DGMR.nowcast_full_frame` / `DGMR.sample` with one member,
     which `NowcastVerifier`, `SpectrumVerifier` and `ValueVerifier` take as they are (`num_members=1`).
 
@@ -349,6 +351,121 @@ def advect_series(x: torch.Tensor, field: torch.Tensor, origin: float = 0.0, spa
              fs, field_group, n, h, w, int(field.shape[1]), int(field.shape[2]), float(origin), float(spacing), steps, out.data_ptr(),
              int(out.stride(0)) if n > 1 else 0, int(out.stride(1)) if steps > 1 else h * w, _stream(device))
     return out
+
+
+def advect_series_perturbed_reference(x, field, direction, amplitude, origin: float = 0.0, spacing: float = 1.0,
+                                      field_group: int = 1) -> np.ndarray:
+    """The specification of `dgmr_advect_series_perturbed`, in float64 numpy -> float64 [N, T, H, W]: `advect_series_reference` with
+    a velocity error per plane and lead time, along and across the local motion.
+
+    x, field: as in `advect_series_reference`.  direction: [field's shape] = (uy, ux), unit vectors or (0, 0) (`unit_directions`),
+    interpolated like the field; amplitude: [N, T, 2] = (a_par, a_perp) in pixels per step.  All inputs are rounded to fp32 first.
+    At q = p - D_(t-1)(p):  v' = v(q) + a_par[n, t] u(q) + a_perp[n, t] (-ux(q), uy(q));  D_t = D_(t-1) + v'(q);
+    out[n, t - 1][p] = s_t(p - D_t(p))."""
+    x = np.asarray(x, dtype=np.float32)
+    field = np.asarray(field, dtype=np.float32).astype(np.float64)
+    direction = np.asarray(direction, dtype=np.float32).astype(np.float64)
+    amplitude = np.asarray(amplitude, dtype=np.float32).astype(np.float64)
+    field_group = int(field_group)
+    if x.ndim != 4 or field.ndim != 4 or field.shape[-1] != 2 or field_group < 1 or x.shape[0] % field_group or \
+            field.shape[0] not in (1, x.shape[0] // field_group):
+        raise ValueError(f"x must be [N, T, H, W] and field [N / {field_group} or 1, Gy, Gx, 2], got {x.shape} and {field.shape}")
+    if direction.shape != field.shape:
+        raise ValueError(f"direction must have the field's shape {field.shape}, got {direction.shape}")
+    n, steps, h, w = x.shape
+    if amplitude.shape != (n, steps, 2):
+        raise ValueError(f"amplitude must be [{n}, {steps}, 2], got {amplitude.shape}")
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if not spacing > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    origin, spacing = float(np.float32(origin)), float(np.float32(spacing))
+    with np.errstate(invalid="ignore"):
+        x = np.where(x >= 0, x, np.float32(0)).astype(np.float64)
+    py, px = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    out = np.empty((n, steps, h, w))
+    for i in range(n):
+        plane = i // field_group if field.shape[0] > 1 else 0
+        f, d = field[plane], direction[plane]
+        dy, dx = np.zeros((h, w)), np.zeros((h, w))
+        for t in range(steps):
+            v = _field_at(f, py - dy, px - dx, origin, spacing)
+            u = _field_at(d, py - dy, px - dx, origin, spacing)
+            a_par, a_perp = amplitude[i, t]
+            dy = dy + (v[..., 0] + (a_par * u[..., 0] - a_perp * u[..., 1]))
+            dx = dx + (v[..., 1] + (a_par * u[..., 1] + a_perp * u[..., 0]))
+            out[i, t] = _sample(x[i, t], py - dy, px - dx)
+    return out
+
+
+def advect_series_perturbed(x: torch.Tensor, field: torch.Tensor, direction: torch.Tensor, amplitude: torch.Tensor, origin: float = 0.0,
+                            spacing: float = 1.0, field_group: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`advect_series_perturbed_reference` for torch tensors -> fp32 [N, T, H, W] on the inputs' device.
+
+    x, field, out: `advect_series`'s layouts and rules.  direction: fp32 of the field's shape on its device (`unit_directions(field)`);
+    amplitude: fp32 [N, T, 2] = (a_par, a_perp) in pixels per step on the device (copied if not contiguous).  On a HIP device one
+    `dgmr_advect_series_perturbed` on the current stream, nothing synchronised; on the CPU the float64 reference, rounded."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"x must be a float32 [N, T, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, steps, h, w = (int(v) for v in x.shape)
+    field_group = int(field_group)
+    if field_group < 1 or n % field_group:
+        raise ValueError(f"field_group={field_group} must divide N={n}")
+    planes = n // field_group
+    if field.dim() != 4 or field.shape[-1] != 2 or field.shape[0] not in (1, planes) or field.dtype != torch.float32 or field.device != x.device:
+        raise ValueError(f"field must be a float32 [{planes} or 1, Gy, Gx, 2] tensor on {x.device}, got {field.dtype} {tuple(field.shape)}")
+    if tuple(direction.shape) != tuple(field.shape) or direction.dtype != torch.float32 or direction.device != x.device:
+        raise ValueError(f"direction must be a float32 {tuple(field.shape)} tensor on {x.device} like the field, got {direction.dtype} "
+                         f"{tuple(direction.shape)} on {direction.device}")
+    if tuple(amplitude.shape) != (n, steps, 2) or amplitude.dtype != torch.float32 or amplitude.device != x.device:
+        raise ValueError(f"amplitude must be a float32 [{n}, {steps}, 2] tensor on {x.device}, got {amplitude.dtype} "
+                         f"{tuple(amplitude.shape)} on {amplitude.device}")
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"T={steps}, 1 ... {MAX_STEPS} are supported")
+    if not float(spacing) > 0:
+        raise ValueError(f"spacing={spacing} must be positive")
+    if out is None:
+        out = torch.empty((n, steps, h, w), dtype=torch.float32, device=x.device)
+    elif (tuple(out.shape) != (n, steps, h, w) or out.dtype != torch.float32 or out.device != x.device or (w > 1 and out.stride(3) != 1)
+          or (h > 1 and out.stride(2) != w) or (n > 1 and out.stride(0) < 0) or (steps > 1 and out.stride(1) < h * w)):
+        raise ValueError(f"out must be a float32 [{n}, {steps}, {h}, {w}] tensor on {x.device} with contiguous planes")
+    if not x.is_cuda:
+        ref = advect_series_perturbed_reference(x.numpy(), field.numpy(), direction.numpy(), amplitude.numpy(), origin, spacing, field_group)
+        out.copy_(torch.from_numpy(ref.astype(np.float32)))
+        return out
+    from ._lib import call
+
+    if (w > 1 and x.stride(3) != 1) or (h > 1 and x.stride(2) != w) or (n > 1 and x.stride(0) < 0) or (steps > 1 and x.stride(1) < 0):
+        x = x.contiguous()
+    if not field[0].is_contiguous() or (field.shape[0] > 1 and field.stride(0) < 0):
+        field = field.contiguous()
+    if not direction[0].is_contiguous() or (direction.shape[0] > 1 and direction.stride(0) < 0):
+        direction = direction.contiguous()
+    amplitude = amplitude.contiguous()
+    fs = int(field.stride(0)) if field.shape[0] > 1 else 0
+    ds = int(direction.stride(0)) if direction.shape[0] > 1 else 0
+    device = x.device
+    with torch.cuda.device(device):
+        call("dgmr_advect_series_perturbed", x.data_ptr(), int(x.stride(0)) if n > 1 else 0, int(x.stride(1)) if steps > 1 else 0,
+             field.data_ptr(), fs, direction.data_ptr(), ds, amplitude.data_ptr(), field_group, n, h, w, int(field.shape[1]),
+             int(field.shape[2]), float(origin), float(spacing), steps, out.data_ptr(), int(out.stride(0)) if n > 1 else 0,
+             int(out.stride(1)) if steps > 1 else h * w, _stream(device))
+    return out
+
+
+def unit_directions(field: torch.Tensor, floor: float = 0.0) -> torch.Tensor:
+    """The direction of motion per lattice node -> fp32 of `field`'s shape ([..., 2] = (vy, vx)): v / |v|, formed in float64 and rounded
+    once; (0, 0) where |v| <= floor or a component is not finite - a calm or unusable node is not perturbed
+    (`advect_series_perturbed`).  torch on the lattice, the same code for CPU and HIP tensors, like `motion_field`."""
+    if field.dim() < 1 or field.shape[-1] != 2 or not field.dtype.is_floating_point:
+        raise ValueError(f"field must be a floating-point [..., 2] tensor, got {field.dtype} {tuple(field.shape)}")
+    if not float(floor) >= 0:
+        raise ValueError(f"floor={floor} must not be negative")
+    v = field.to(torch.float64)
+    norm = torch.sqrt((v * v).sum(dim=-1, keepdim=True))
+    ok = torch.isfinite(v).all(dim=-1, keepdim=True) & (norm > float(floor))
+    u = torch.where(ok, v, torch.zeros_like(v)) / torch.where(ok, norm, torch.ones_like(norm))
+    return u.to(torch.float32).contiguous()
 
 
 # ---- motion field ----------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // The advection baseline on the device (advection.py): block-matching motion between two frames (dgmr_block_match) and the
 // semi-Lagrangian extrapolation of a frame along a motion field for all lead times (dgmr_advect; dgmr_advect_series: the same with a
-// source of its own per lead time and one field plane per group of planes - stochastic.py's ensemble members).
+// source of its own per lead time and one field plane per group of planes - stochastic.py's ensemble members;
+// dgmr_advect_series_perturbed: that with a velocity error per plane and lead time along and across the local motion).
 //
 // Block matching.  One workgroup per (plane, block).  The `next` block (B x B) is staged in LDS first and its wet elements are
 // counted on the way; a dry block - most of a radar frame - writes its five +inf and leaves before the search window of `prev`
@@ -27,6 +28,18 @@
 // A source tap is fmaf(f, b - a, a) as well: f = 0 returns a itself, so an integer displacement copies the source bit for bit, and
 // the interpolation's own rounding is at most 4 * 2^-24 * max|x| (two one-axis interpolations of 2 * 2^-24 each, blended, plus the
 // blend's subtraction and fma).
+//
+// Perturbed velocities (dgmr_advect_series_perturbed).  A second lattice of the field's geometry holds directions (uy, ux), which
+// the host has normalised - the kernel has no division of its own, no square root and no transcendental - and every plane n and
+// lead time t has an amplitude pair (a_par, a_perp), loaded once per step by each thread with its own n (a workgroup may straddle
+// two planes).  At q = p - D, with the field's node indices i0 / i1 and weights f for both lattices, in this order:
+//   (vy, vx) = bilinear(field)(q)                         as above
+//   (uy, ux) = bilinear(direction)(q)                     lerp_fma, x then y, as for the field
+//   vy' = fmaf(a_par, uy, fmaf(a_perp, -ux, vy))          the perpendicular of (uy, ux) is (-ux, uy)
+//   vx' = fmaf(a_par, ux, fmaf(a_perp,  uy, vx))
+//   D = D + v';  out[n, t][p] = s_t(p - D)
+// An axis of v' takes both components of the direction: 2 x 6 rounded operations for their interpolations and 2 for the fmas, 14 on
+// top of the 10 per step - (10 + 14) per step + 1, on two axes - c' = 50.  a = 0 returns v itself (fmaf(0, u, v) = v for finite u).
 #include "common.h"
 
 namespace {
@@ -164,6 +177,10 @@ struct AdvGeom {
     float origin, spacing;
     int64_t x_step_stride;  // dgmr_advect_series: the source of lead time t is x + (t - 1) x_step_stride ...
     int field_group;        // ... and plane n reads field plane n / field_group
+    // dgmr_advect_series_perturbed: the direction lattice (the field's geometry and plane mapping) and amplitude[n][t][2] = (a_par, a_perp)
+    const float* direction;
+    const float* amplitude;
+    int64_t direction_plane_stride;
 };
 
 // lattice coordinate of pixel coordinate q on an axis of G nodes -> the lower node i0, the upper node i1 and the weight of i1
@@ -193,9 +210,11 @@ __device__ __forceinline__ float source_sample(const float* __restrict__ x, int 
     return lerp_fma(top, bot, fy);
 }
 
-// SERIES = false is dgmr_advect as it always was; SERIES = true adds the per-step source and the shared field plane, nothing else
-template <int V, bool SERIES>
+// SERIES = false is dgmr_advect as it always was; SERIES = true adds the per-step source and the shared field plane, nothing else;
+// PERTURBED (with SERIES) adds the direction taps and the two fmas per axis, nothing else
+template <int V, bool SERIES, bool PERTURBED = false>
 __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
+    static_assert(SERIES || !PERTURBED, "the perturbed kernel is a series kernel");
     const int64_t item = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (item >= g.items) return;
     const int WV = g.W / V;
@@ -206,12 +225,20 @@ __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
     const float* __restrict__ x = g.x + n * g.x_plane_stride;
     const float* __restrict__ fld = g.field + (SERIES ? n / g.field_group : n) * g.field_plane_stride;
     float* __restrict__ o = g.out + n * g.out_plane_stride + (int64_t)y * g.W + xq;
+    const float* __restrict__ dir = nullptr;
+    const float* __restrict__ amp = nullptr;
+    if constexpr (PERTURBED) {
+        dir = g.direction + (n / g.field_group) * g.direction_plane_stride;
+        amp = g.amplitude + n * g.T * 2;  // n < 2^24, T <= 64
+    }
     const float py = (float)y;
     float Dy[V], Dx[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) Dy[k] = 0.f, Dx[k] = 0.f;
     for (int t = 0; t < g.T; ++t) {
         float r[V];
+        float a_par = 0.f, a_perp = 0.f;
+        if constexpr (PERTURBED) a_par = amp[2 * t], a_perp = amp[2 * t + 1];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const float px = (float)(xq + k);
@@ -223,8 +250,18 @@ __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
             const float* b = fld + ((int64_t)y0 * g.Gx + x1) * 2;
             const float* c = fld + ((int64_t)y1 * g.Gx + x0) * 2;
             const float* d = fld + ((int64_t)y1 * g.Gx + x1) * 2;
-            const float vy = lerp_fma(lerp_fma(a[0], b[0], fx), lerp_fma(c[0], d[0], fx), fy);
-            const float vx = lerp_fma(lerp_fma(a[1], b[1], fx), lerp_fma(c[1], d[1], fx), fy);
+            float vy = lerp_fma(lerp_fma(a[0], b[0], fx), lerp_fma(c[0], d[0], fx), fy);
+            float vx = lerp_fma(lerp_fma(a[1], b[1], fx), lerp_fma(c[1], d[1], fx), fy);
+            if constexpr (PERTURBED) {
+                const float* da = dir + ((int64_t)y0 * g.Gx + x0) * 2;
+                const float* db = dir + ((int64_t)y0 * g.Gx + x1) * 2;
+                const float* dc = dir + ((int64_t)y1 * g.Gx + x0) * 2;
+                const float* dd = dir + ((int64_t)y1 * g.Gx + x1) * 2;
+                const float uy = lerp_fma(lerp_fma(da[0], db[0], fx), lerp_fma(dc[0], dd[0], fx), fy);
+                const float ux = lerp_fma(lerp_fma(da[1], db[1], fx), lerp_fma(dc[1], dd[1], fx), fy);
+                vy = fmaf(a_par, uy, fmaf(a_perp, -ux, vy));
+                vx = fmaf(a_par, ux, fmaf(a_perp, uy, vx));
+            }
             Dy[k] += vy;
             Dx[k] += vx;
             r[k] = source_sample(SERIES ? x + (int64_t)t * g.x_step_stride : x, g.H, g.W, py - Dy[k], px - Dx[k]);
@@ -292,7 +329,7 @@ extern "C" int dgmr_advect(const float* x, int64_t x_plane_stride, const float* 
     const int64_t items = N * H * (W / V);
     DGMR_CHECK_ARG(items <= (1ll << 38), "%s: %lld pixels are out of range", fn, (long long)(N * H * W));
     const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing,
-                    0, 1};
+                    0, 1, nullptr, nullptr, 0};
     const dim3 grid((unsigned)((items + 255) / 256)), threads(256);
     if (wide)
         hipLaunchKernelGGL((advect_kernel<4, false>), grid, threads, 0, ST, g);
@@ -327,12 +364,51 @@ extern "C" int dgmr_advect_series(const float* x, int64_t x_plane_stride, int64_
     const int64_t items = N * H * (W / V);
     DGMR_CHECK_ARG(items <= (1ll << 38), "%s: %lld pixels are out of range", fn, (long long)(N * H * W));
     const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing,
-                    x_step_stride, field_group};
+                    x_step_stride, field_group, nullptr, nullptr, 0};
     const dim3 grid((unsigned)((items + 255) / 256)), threads(256);
     if (wide)
         hipLaunchKernelGGL((advect_kernel<4, true>), grid, threads, 0, ST, g);
     else
         hipLaunchKernelGGL((advect_kernel<1, true>), grid, threads, 0, ST, g);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dgmr_advect_series_perturbed(const float* x, int64_t x_plane_stride, int64_t x_step_stride, const float* field,
+                                            int64_t field_plane_stride, const float* direction, int64_t direction_plane_stride,
+                                            const float* amplitude, int field_group, int64_t N, int H, int W, int Gy, int Gx, float origin,
+                                            float spacing, int T, float* out, int64_t out_plane_stride, int64_t out_step_stride, void* stream) {
+    const char* fn = "dgmr_advect_series_perturbed";
+    DGMR_CHECK_ARG(x && field && out, "%s: null pointer", fn);
+    DGMR_CHECK_ARG(direction && amplitude, "%s: null direction or amplitude", fn);
+    DGMR_CHECK_ARG(T >= 1 && T <= 64, "%s: T=%d lead times, 1 ... 64 are supported", fn, T);
+    DGMR_CHECK_ARG(spacing > 0.f && spacing <= 3.0e38f && origin == origin && origin >= -3.0e38f && origin <= 3.0e38f,
+                   "%s: spacing=%g must be positive and finite, origin=%g finite", fn, (double)spacing, (double)origin);
+    DGMR_CHECK_ARG(Gy >= 1 && Gx >= 1 && (int64_t)Gy * Gx <= (1 << 28), "%s: a lattice of %d x %d nodes is out of range", fn, Gy, Gx);
+    DGMR_CHECK_ARG(N >= 1 && N <= (1 << 24), "%s: N=%lld planes out of range", fn, (long long)N);
+    DGMR_CHECK_ARG(field_group >= 1, "%s: field_group=%d must be at least 1", fn, field_group);
+    DGMR_CHECK_ARG(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(x_plane_stride >= 0 && x_plane_stride <= INT64_MAX / 4 / N && field_plane_stride >= 0 &&
+                       field_plane_stride <= INT64_MAX / 4 / N && x_step_stride >= 0 && x_step_stride <= INT64_MAX / 4 / 64,
+                   "%s: x_plane_stride=%lld, x_step_stride=%lld or field_plane_stride=%lld out of range", fn, (long long)x_plane_stride,
+                   (long long)x_step_stride, (long long)field_plane_stride);
+    DGMR_CHECK_ARG(direction_plane_stride >= 0 && direction_plane_stride <= INT64_MAX / 4 / N, "%s: direction_plane_stride=%lld out of range",
+                   fn, (long long)direction_plane_stride);
+    DGMR_CHECK_ARG(out_plane_stride >= 0 && out_plane_stride <= INT64_MAX / 4 / N && (T == 1 || out_step_stride >= (int64_t)H * W) &&
+                       out_step_stride >= 0 && out_step_stride <= INT64_MAX / 4 / 64,
+                   "%s: out_plane_stride=%lld out of range or out_step_stride=%lld below H * W", fn, (long long)out_plane_stride,
+                   (long long)out_step_stride);
+    const bool wide = W % 4 == 0 && ((uintptr_t)out & 15) == 0 && out_plane_stride % 4 == 0 && out_step_stride % 4 == 0;
+    const int V = wide ? 4 : 1;
+    const int64_t items = N * H * (W / V);
+    DGMR_CHECK_ARG(items <= (1ll << 38), "%s: %lld pixels are out of range", fn, (long long)(N * H * W));
+    const AdvGeom g{x, field, out, x_plane_stride, field_plane_stride, out_plane_stride, out_step_stride, items, H, W, Gy, Gx, T, origin, spacing,
+                    x_step_stride, field_group, direction, amplitude, direction_plane_stride};
+    const dim3 grid((unsigned)((items + 255) / 256)), threads(256);
+    if (wide)
+        hipLaunchKernelGGL((advect_kernel<4, true, true>), grid, threads, 0, ST, g);
+    else
+        hipLaunchKernelGGL((advect_kernel<1, true, true>), grid, threads, 0, ST, g);
     DGMR_CHECK_LAUNCH();
     return 0;
 }

@@ -33,7 +33,12 @@ phi2 X_(t-2) + g A Wh_t, started from the last two frames; `estimate_ar2` adds t
 `ar2_coefficients` solves Yule-Walker per bin (clipped so that the process stays bounded, keeps rho1 and has unit variance);
 `EnsembleAdvectionNowcaster(order=2)` uses them.
 
-Limits: no velocity perturbations; the AR(2) is per radial bin and from coherences, not per cascade level from pixel correlations
+`EnsembleAdvectionNowcaster(...).perturb_velocities("steps")` adds STEPS' perturbed motion vectors: every member draws one error
+along and one across the local motion, which grow with lead time by `velocity_perturbation_scale`'s law, and moves along
+`advection.advect_series_perturbed` instead of `advect_series`.
+
+Limits: a member's velocity error is one pair of scalars along and across the local motion that grows by a fixed law of lead time -
+not a spatially varying perturbation field, and the law is not fitted to this data; the AR(2) is per radial bin and from coherences, not per cascade level from pixel correlations
 as in STEPS, its Yule-Walker solution is ill-conditioned near rho1 = 1, its second state carries the advection's zero inflow at
 the border and its noise amplitude comes from the last frame alone; bilinear advection and motion error bias the estimate's high
 wavenumbers low, and a frame too small to keep a window clear of the margin falls back to the law; the mask's dilation law is
@@ -49,8 +54,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .advection import (CONTEXT_FRAMES, MAX_STEPS, AdvectionNowcaster, _planes, _stream, advect, advect_series, lattice_geometry,
-                        motion_field)
+from .advection import (CONTEXT_FRAMES, MAX_STEPS, AdvectionNowcaster, _planes, _stream, advect, advect_series, advect_series_perturbed,
+                        lattice_geometry, motion_field, unit_directions)
 from .spectra import _radial_bins
 
 WINDOWS = (32, 64, 128)
@@ -692,6 +697,43 @@ def precipitation_mask(z0: torch.Tensor, pad: float, radius: int, growth: float 
     return (torch.cat(planes, dim=1) > 0).to(torch.uint8)
 
 
+# ---- velocity perturbations ------------------------------------------------------------------------------------------------------------
+STEPS_P_PAR = (10.88, 0.23, -7.68)   # pysteps' fitted (a, b, c) of the error along the motion, km/h with t in minutes - quoted from memory
+STEPS_P_PERP = (5.76, 0.31, -2.72)   # ... and across it
+VELOCITY_SEED_OFFSET = 0x56454C  # "VEL": the velocity noise of seed s comes from a CPU generator seeded with s + this
+
+
+def _law(p, what: str):
+    try:
+        a, b, c = (float(v) for v in p)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}={p!r}: three numbers (a, b, c) of a t^b + c are required") from None
+    if not all(np.isfinite(v) for v in (a, b, c)):
+        raise ValueError(f"{what}={p!r} must be finite")
+    return a, b, c
+
+
+def velocity_perturbation_scale(steps: int, timestep: float = 5.0, km_per_pixel: float = 1.0, p_par=STEPS_P_PAR,
+                                p_perp=STEPS_P_PERP) -> torch.Tensor:
+    """The standard deviation of a member's velocity error per lead time -> fp32 [steps, 2] = (sigma_par, sigma_perp) in pixels per step,
+    computed in float64 and rounded once:  sigma[t] = max(a ((t + 1) timestep)^b + c, 0) timestep / 60 / km_per_pixel,  t = 0 ...
+    steps - 1, with (a, b, c) = p_par along the motion and p_perp across it: STEPS' law a t^b + c in km/h with t in minutes
+    (timestep: minutes per step), clipped at 0 and taken to pixels per step.  The defaults are pysteps' fitted constants quoted from
+    memory, not fitted to any data set here."""
+    steps = int(steps)
+    if not 1 <= steps <= MAX_STEPS:
+        raise ValueError(f"steps={steps}, 1 ... {MAX_STEPS} are supported")
+    if not (float(timestep) > 0 and float(km_per_pixel) > 0 and np.isfinite(timestep) and np.isfinite(km_per_pixel)):
+        raise ValueError(f"timestep={timestep} and km_per_pixel={km_per_pixel} must be positive and finite")
+    minutes = (np.arange(steps, dtype=np.float64) + 1.0) * float(timestep)
+    sigma = np.stack([np.maximum(a * minutes ** b + c, 0.0) for a, b, c in (_law(p_par, "p_par"), _law(p_perp, "p_perp"))], axis=1)
+    with np.errstate(over="ignore"):
+        sigma = (sigma * float(timestep) / 60.0 / float(km_per_pixel)).astype(np.float32)
+    if not np.isfinite(sigma).all():
+        raise ValueError(f"p_par={p_par!r}, p_perp={p_perp!r}: the law leaves fp32's range within {steps} steps")
+    return torch.from_numpy(sigma)
+
+
 class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     """`AdvectionNowcaster` with `num_members` stochastic members: the last frame in dB evolves per window and Fourier mode by
     `spectral_ar` in Lagrangian coordinates, every member is then moved along the context's motion field (`advect_series`, the
@@ -707,13 +749,20 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     one step along the motion field.  order=2 takes rho="estimate" (`estimate_ar2` per call: `last_rho`, `last_rho2` fp32
     [planes, window], `last_coef` fp32 [planes, 3, window], `last_windows`) or an fp32 [2, window] tensor (rho1, rho2)
     (`ar2_coefficients` once: `last_coef` fp32 [3, window]); rho=None is refused - the law has no second lag.  Either way one
-    `spectral_ar2` covers all planes."""
+    `spectral_ar2` covers all planes.
+    Velocity perturbations are off after construction - the members of a case all move along the one motion field (`advect_series`);
+    `perturb_velocities("steps")` or `perturb_velocities((p_par, p_perp))` switches STEPS' perturbed motion vectors on: member m of
+    a plane draws one pair (eps_par, eps_perp) of unit Gaussians, its velocity at lead time t is v + eps_par sigma_par[t] u +
+    eps_perp sigma_perp[t] u_perp with u = `unit_directions(last_field)` and sigma = `velocity_scale` (fp32 [T, 2],
+    `velocity_perturbation_scale`), and one `advect_series_perturbed` moves all members.  The pairs of the latest call are
+    `last_velocity_noise` (fp32 [planes, M, 2])."""
 
     def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
                  min_wet: Optional[int] = None, smooth: int = 2, window: int = 128, threshold: float = 0.1, pad: float = 5.0,
                  rho: Optional[torch.Tensor] = None, order: int = 1, probability_matching: bool = False,
                  mask_radius: Optional[int] = None, mask_growth: float = 0.0):
         super().__init__(forecast_steps, block, stride, radius, wet_threshold, min_wet, smooth)
+        self.velocity_scale = self.last_velocity_noise = None
         # order sits beside rho, which it qualifies; a bool here is a positional probability_matching from before it existed
         if isinstance(order, bool) or order not in (1, 2):
             raise ValueError(f"order={order!r}: 1 (an AR(1) per mode) or 2 (an AR(2)) is required; pass the arguments after rho by keyword")
@@ -750,7 +799,40 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         gen.manual_seed(int(seed))
         return torch.randn((planes, int(num_members), self.forecast_steps, h, w), generator=gen, device=device, dtype=torch.float32)
 
-    def _members(self, context: torch.Tensor, num_members: int, seed: int, white: Optional[torch.Tensor]) -> torch.Tensor:
+    def perturb_velocities(self, velocity_perturbation="steps", timestep: float = 5.0, km_per_pixel: float = 1.0):
+        """Switch the members' velocity perturbations on or off -> self, for `EnsembleAdvectionNowcaster(...).perturb_velocities()`.
+        velocity_perturbation: None (off: `advect_series`, the members of a case move along one motion field), "steps" (the defaults of
+        `velocity_perturbation_scale`) or a pair (p_par, p_perp) of (a, b, c) triples; timestep: minutes per step; km_per_pixel: the
+        grid's.  Sets `velocity_scale` = `velocity_perturbation_scale(forecast_steps, timestep, km_per_pixel, p_par, p_perp)`, fp32
+        [T, 2], or None.  (A method, not constructor arguments: the constructor's positional order ends with the mask's arguments.)"""
+        if velocity_perturbation is None:
+            self.velocity_scale = None
+            return self
+        if isinstance(velocity_perturbation, str):
+            if velocity_perturbation != "steps":
+                raise ValueError(f"velocity_perturbation={velocity_perturbation!r}: None, \"steps\" or a pair (p_par, p_perp) is required")
+            laws = (STEPS_P_PAR, STEPS_P_PERP)
+        else:
+            try:
+                laws = tuple(velocity_perturbation)
+            except TypeError:
+                laws = ()
+            if len(laws) != 2:
+                raise ValueError(f"velocity_perturbation={velocity_perturbation!r}: None, \"steps\" or a pair (p_par, p_perp) of "
+                                 "(a, b, c) triples is required")
+        self.velocity_scale = velocity_perturbation_scale(self.forecast_steps, timestep, km_per_pixel, laws[0], laws[1])
+        return self
+
+    def velocity_noise(self, planes: int, num_members: int, seed: int = 0) -> torch.Tensor:
+        """The members' (eps_par, eps_perp) that `nowcast` draws for `seed`: fp32 [planes, M, 2] unit Gaussians on the CPU, from a
+        second `torch.Generator` - a CPU one, seeded with (seed + VELOCITY_SEED_OFFSET) mod 2^63, so that a seed gives the same
+        pairs for every device and the white-noise draw of `seed` is what it is without perturbations."""
+        gen = torch.Generator()
+        gen.manual_seed((int(seed) + VELOCITY_SEED_OFFSET) % (1 << 63))
+        return torch.randn((int(planes), int(num_members), 2), generator=gen, dtype=torch.float32)
+
+    def _members(self, context: torch.Tensor, num_members: int, seed: int, white: Optional[torch.Tensor],
+                 velocity_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """context [T_in, P, H, W] -> rain rates fp32 [P, M, T, H, W]"""
         num_members = int(num_members)
         if num_members < 1:
@@ -758,6 +840,16 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
         planes, h, w = (int(v) for v in context.shape[1:])
         _check_plane(h, w, self.window)
         shape = (planes, num_members, self.forecast_steps, h, w)
+        if self.velocity_scale is None:
+            if velocity_noise is not None:
+                raise ValueError("velocity_noise needs perturb_velocities(...) first")
+        elif velocity_noise is None:
+            velocity_noise = self.velocity_noise(planes, num_members, seed)
+        elif not isinstance(velocity_noise, torch.Tensor) or tuple(velocity_noise.shape) != (planes, num_members, 2) or \
+                velocity_noise.dtype != torch.float32:
+            raise ValueError(f"velocity_noise must be a float32 [{planes}, {num_members}, 2] tensor, got "
+                             f"{getattr(velocity_noise, 'dtype', type(velocity_noise))} {tuple(getattr(velocity_noise, 'shape', ()))}")
+        self.last_velocity_noise = None if velocity_noise is None else velocity_noise.to(context.device)
         if white is None:
             white = self.white_noise(planes, num_members, h, w, context.device, seed)
         elif tuple(white.shape) != shape or white.dtype != torch.float32 or white.device != context.device:
@@ -788,26 +880,36 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
             if self.mask_radius is not None:
                 mask = precipitation_mask(z0, self.pad, self.mask_radius, self.mask_growth, self.forecast_steps)
             probability_match(z, z0, mask, out=z)
-        moved = advect_series(z.view(planes * num_members, self.forecast_steps, h, w), self.last_field, origin, spacing,
-                              field_group=num_members)
+        if self.velocity_scale is None:
+            moved = advect_series(z.view(planes * num_members, self.forecast_steps, h, w), self.last_field, origin, spacing,
+                                  field_group=num_members)
+        else:  # amplitude[n = plane M + m, t] = eps[plane, m] sigma[t], one fp32 product each
+            amplitude = self.last_velocity_noise[:, :, None, :] * self.velocity_scale.to(context.device)[None, None, :, :]
+            moved = advect_series_perturbed(z.view(planes * num_members, self.forecast_steps, h, w), self.last_field,
+                                            unit_directions(self.last_field), amplitude.reshape(planes * num_members, self.forecast_steps, 2),
+                                            origin, spacing, field_group=num_members)
         return from_db(moved, self.threshold, self.pad).view(shape)
 
     def nowcast(self, frames, num_members: int, seed: int = 0, white: Optional[torch.Tensor] = None, scale: float = 1.0,
-                offset: float = 0.0) -> torch.Tensor:
+                offset: float = 0.0, velocity_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """frames [T_in >= 2, H, W, C] as in `AdvectionNowcaster.nowcast` -> fp32 [M, forecast_steps, C, H, W] on the frames' device.
-        seed: of the white noise; white: fp32 [C, M, T, H, W] to use instead (the same field gives the same members on every device)."""
+        seed: of the white noise; white: fp32 [C, M, T, H, W] to use instead (the same field gives the same members on every device).
+        velocity_noise (after `perturb_velocities`): fp32 [C, M, 2] = the members' (eps_par, eps_perp) on any device, to use instead
+        of `self.velocity_noise(C, M, seed)`; kept as `last_velocity_noise`."""
         from .verification import observed_from_frames
 
         x = observed_from_frames(frames, scale, offset)  # [T_in, C, H, W]
         if x.shape[0] < 2:
             raise ValueError(f"frames holds {x.shape[0]} frames, the motion needs 2")
-        return self._members(x.contiguous(), num_members, seed, white).permute(1, 2, 0, 3, 4).contiguous()
+        return self._members(x.contiguous(), num_members, seed, white, velocity_noise).permute(1, 2, 0, 3, 4).contiguous()
 
-    def nowcast_batch(self, images: torch.Tensor, num_members: int, seed: int = 0, white: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """images fp32 [B, T_in >= 2, C, H, W] -> fp32 [M, B, forecast_steps, C, H, W].  white: fp32 [B * C, M, T, H, W]."""
+    def nowcast_batch(self, images: torch.Tensor, num_members: int, seed: int = 0, white: Optional[torch.Tensor] = None,
+                      velocity_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """images fp32 [B, T_in >= 2, C, H, W] -> fp32 [M, B, forecast_steps, C, H, W].  white: fp32 [B * C, M, T, H, W];
+        velocity_noise: fp32 [B * C, M, 2] (`nowcast`)."""
         if images.dim() != 5 or images.shape[1] < 2 or images.dtype != torch.float32:
             raise ValueError(f"images must be a float32 [B, T_in >= 2, C, H, W] tensor, got {images.dtype} {tuple(images.shape)}")
         b, _, c, h, w = images.shape
         context = images[:, -CONTEXT_FRAMES:].permute(1, 0, 2, 3, 4).reshape(-1, b * c, h, w).contiguous()
-        rain = self._members(context, num_members, seed, white)  # [B * C, M, T, H, W]
+        rain = self._members(context, num_members, seed, white, velocity_noise)  # [B * C, M, T, H, W]
         return rain.view(b, c, int(num_members), self.forecast_steps, h, w).permute(2, 0, 3, 1, 4, 5).contiguous()

@@ -1,7 +1,7 @@
 """Device time of the stochastic advection ensemble on a full 1536 x 1280 composite (skillful_nowcasting_amd/stochastic.py;
 dgmr_spectral_ar in csrc/spectral_ar.hip, dgmr_advect_series in csrc/advect.hip).
 
-    python tools/stochastic_timing.py [--repeats 7] [--order 2] [--out profiles/stochastic_timing.json]
+    python tools/stochastic_timing.py [--repeats 7] [--order 2] [--velocity] [--out profiles/stochastic_timing.json]
                                       [--match-out profiles/probability_match_timing.json]
 
 Inputs: the rain-covered sequence of tools/advection_timing.py (a smooth field moving by (2, -3) pixels per frame), M = 8 members,
@@ -24,6 +24,11 @@ With --order 2 also (dgmr_spectral_ar2 in csrc/spectral_ar.hip), in the --out fi
   * spectral_ar2 beside spectral_ar on the same inputs (zm1: the frame before the last moved one step; rho2 = rho^3), and the
     same recursion written with torch.fft;
   * the whole nowcast at order 2 beside order 1, with explicit correlations and with rho="estimate".
+With --velocity also (dgmr_advect_series_perturbed in csrc/advect.hip), under "velocity" in the --out file (default
+profiles/velocity_perturbation_timing.json), every group timed in alternation, one call of each per round:
+  * advect_series beside advect_series_perturbed with zero amplitudes (and whether the two results have the same bits) and with the
+    amplitudes of perturb_velocities("steps") for seed 0;
+  * the whole order-1 nowcast without and with perturb_velocities("steps").
 Numbers are recorded, not asserted."""
 import argparse
 import json
@@ -52,6 +57,26 @@ def timed(fn, repeats):
         t1.synchronize()
         times.append(t0.elapsed_time(t1))
     return {"ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "calls": len(times)}
+
+
+def timed_alternating(fns, repeats):
+    """`timed` for several calls that are to be compared: after a warm-up of each, `repeats` rounds that run every call once, one after
+    the other, so that a drift of the machine reaches all of them alike -> {name: `timed`'s record}"""
+    import torch
+
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            fn()
+            t1.record()
+            t1.synchronize()
+            times[k].append(t0.elapsed_time(t1))
+    return {k: {"ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "calls": len(v)} for k, v in times.items()}
 
 
 def spectral_ar_torch(z0, white, rho, window):
@@ -147,7 +172,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--match-out", default=None)
     ap.add_argument("--order", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--velocity", action="store_true")
     a = ap.parse_args()
+    if a.velocity and not a.out:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "velocity_perturbation_timing.json")
     import torch
 
     import __graft_entry__ as g
@@ -162,7 +190,8 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(0)
     seq = rain_sequence(gen, dev, 4, (2, -3), False)  # [4, H, W]
     rec = {"device": torch.cuda.get_device_name(0),
-           "command": f"python tools/stochastic_timing.py --repeats {a.repeats}" + (" --order 2" if a.order == 2 else ""), "frame": [H, W],
+           "command": f"python tools/stochastic_timing.py --repeats {a.repeats}" + (" --order 2" if a.order == 2 else "")
+           + (" --velocity" if a.velocity else ""), "frame": [H, W],
            "members": MEMBERS, "lead_times": T_OUT, "window": WINDOW, "assumed_rates": {"copy_bytes_per_s": COPY_BYTES_PER_S},
            "wet_pixel_share": float((seq > 0).double().mean())}
     nowcaster = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW)
@@ -229,6 +258,34 @@ def main():
     adv.update({"bytes_stored": plane, "GB_per_s_stored": plane / adv["ms"] / 1e6, "ms_at_copy_rate": 2 * plane / COPY_BYTES_PER_S * 1e3})
     rec["advect_series"] = adv
     print(f"advect_series {MEMBERS} x {T_OUT} planes: {adv['ms']:.3f} ms ({adv['GB_per_s_stored']:.0f} GB/s stored)", flush=True)
+    if a.velocity:
+        from skillful_nowcasting_amd.advection import advect_series_perturbed, unit_directions
+        from skillful_nowcasting_amd.stochastic import velocity_perturbation_scale
+
+        direction = unit_directions(field)
+        sigma = velocity_perturbation_scale(T_OUT).to(dev)
+        eps = nowcaster.velocity_noise(1, MEMBERS, 0).to(dev)
+        amps = {"zero": torch.zeros(MEMBERS, T_OUT, 2, device=dev),
+                "steps": (eps[:, :, None, :] * sigma[None, None]).reshape(MEMBERS, T_OUT, 2).contiguous()}
+        moved_p = torch.empty_like(moved)
+        advect_series(out[0], field, origin, spacing, field_group=MEMBERS, out=moved)
+        advect_series_perturbed(out[0], field, direction, amps["zero"], origin, spacing, field_group=MEMBERS, out=moved_p)
+        same = bool(torch.equal(moved.view(torch.int32), moved_p.view(torch.int32)))
+        fns = {"advect_series": lambda: advect_series(out[0], field, origin, spacing, field_group=MEMBERS, out=moved)}
+        for key, amp in amps.items():
+            fns["advect_series_perturbed_" + key] = (lambda amp=amp: advect_series_perturbed(out[0], field, direction, amp, origin, spacing,
+                                                                                           field_group=MEMBERS, out=moved_p))
+        vel = timed_alternating(fns, a.repeats)
+        for key in amps:
+            vel["advect_series_perturbed_" + key]["over_advect_series"] = vel["advect_series_perturbed_" + key]["ms"] / vel["advect_series"]["ms"]
+        vel["zero_amplitude_gives_advect_series_bits"] = same
+        vel["largest_amplitude_px_per_step"] = float(amps["steps"].abs().max())
+        rec["velocity"] = vel
+        print(f"alternating: advect_series {vel['advect_series']['ms']:.3f} ms ({vel['advect_series']['min_ms']:.3f} - "
+              f"{vel['advect_series']['max_ms']:.3f}); perturbed with zero amplitudes {vel['advect_series_perturbed_zero']['ms']:.3f} ms "
+              f"({vel['advect_series_perturbed_zero']['over_advect_series']:.2f} x, the same bits: {same}), with \"steps\" amplitudes "
+              f"{vel['advect_series_perturbed_steps']['ms']:.3f} ms ({vel['advect_series_perturbed_steps']['over_advect_series']:.2f} x)", flush=True)
+        del moved_p
     del moved, white
     match = None
     if a.match_out:
@@ -256,6 +313,15 @@ def main():
     frames = seq[..., None].contiguous()
     rec["nowcast"] = timed(lambda: nowcaster.nowcast(frames, MEMBERS, seed=1), a.repeats)
     print(f"whole nowcast: {rec['nowcast']['ms']:.3f} ms", flush=True)
+    if a.velocity:
+        perturbed = EnsembleAdvectionNowcaster(forecast_steps=T_OUT, window=WINDOW).perturb_velocities("steps")
+        both = timed_alternating({"nowcast": lambda: nowcaster.nowcast(frames, MEMBERS, seed=1),
+                                  "nowcast_perturbed": lambda: perturbed.nowcast(frames, MEMBERS, seed=1)}, a.repeats)
+        both["nowcast_perturbed"]["over_unperturbed"] = both["nowcast_perturbed"]["ms"] / both["nowcast"]["ms"]
+        rec["velocity"].update(both)
+        print(f"alternating: whole nowcast {both['nowcast']['ms']:.3f} ms ({both['nowcast']['min_ms']:.3f} - {both['nowcast']['max_ms']:.3f}), "
+              f"with velocity perturbations {both['nowcast_perturbed']['ms']:.3f} ms ({both['nowcast_perturbed']['over_unperturbed']:.3f} x)",
+              flush=True)
     if a.order == 2:
         for key, kw in (("nowcast_order2", {"rho": rhos.cpu(), "order": 2}), ("nowcast_estimate", {"rho": "estimate"}),
                         ("nowcast_order2_estimate", {"rho": "estimate", "order": 2})):
