@@ -701,6 +701,35 @@ int dgmr_advect(const float* x, int64_t x_plane_stride, const float* field, int6
                 int Gx, float origin, float spacing, int T, float* out, int64_t out_plane_stride, int64_t out_step_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lucas-Kanade refinement of a block match (advection.py: lk_refine, motion_field(subpixel="lk"); csrc/advect.hip).  A new symbol,
+ * same ABI version.
+ *
+ * prev, next, plane_stride, N, H, W, block, stride: dgmr_block_match's, and disp[n][by][bx][2], cost[n][by][bx][5] its results for
+ * them.  Per plane and block with corner (y0, x0) = (by stride, bx stride), integer match d0 = disp and Q = next (missing as 0), over
+ * the block's interior I = {(y0 + i, x0 + j): 1 <= i, j <= block - 2}:
+ *   g = (gy, gx)   central differences of Q, 0.5 (Q[y + 1][x] - Q[y - 1][x]) and the same along x (fp32; every tap inside the block)
+ *   G = sum_I g g^T, (lambda_min, lambda_max) = (tr -+ sqrt(max(tr^2 - 4 det, 0))) / 2 in float64
+ *   the block is conditioned when lambda_min > 0 and lambda_min >= eig_ratio lambda_max
+ *   d = d0; `iterations` times, for a conditioned block:  r(p) = Q(p) - s(p - d), s the bilinear interpolation of prev (a + f (b - a)
+ *     with one fma, x then y, as dgmr_advect; elements outside the frame and missing ones are 0);  b = -sum_I g r;
+ *     delta = G^-1 b (float64, closed form);  d <- clip(d + delta, d0 - 1, d0 + 1) per axis, kept as fp32
+ *   v[n][by][bx][2]      fp32     d (d0 for a block that is not conditioned)
+ *   eig[n][by][bx][2]    float64  (lambda_min, lambda_max)
+ *   residual[n][by][bx]  float64  sum_I r^2 at the final d
+ * A block whose cost[...][0] is not finite is dry: v = (0, 0), eig = (0, 0), residual = +inf, nothing staged.  One workgroup of 256
+ * threads per (plane, block); the block and the (block + 2)^2 window of prev around the match staged in LDS once (d never leaves
+ * d0 +- 1, so no tap leaves the window; any int32 in disp is safe, a window outside the frame reads as 0); every sum is fp32 fmaf
+ * per thread over its at most four pixels, then float64 in a fixed order over lanes and waves - no atomics, two launches give the
+ * same bits.  A match that is exact at an integer (r = 0 on I) returns v = d0 bit for bit and residual = 0.  Supported: block 16 or
+ * 32, 1 <= stride <= block, H, W >= block, N >= 1, 1 <= iterations <= 16, eig_ratio >= 0 and finite; everything else and null
+ * pointers return < 0 and set the error message before anything is enqueued.  No alignment demands.  Runs on `stream`, does not
+ * synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_lk_refine(const float* prev, const float* next, int64_t plane_stride, int64_t N, int H, int W, int block, int stride,
+                   const int32_t* disp, const float* cost, int iterations, float eig_ratio, float* v, double* eig, double* residual,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The stochastic advection ensemble (stochastic.py; csrc/spectral_ar.hip, csrc/advect.hip).  New symbols, same ABI version.
  *
  * dgmr_spectral_ar: an AR(1) process per Fourier mode of overlapping L x L windows, L one of 32, 64, 128, blended to full planes.

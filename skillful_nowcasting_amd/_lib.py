@@ -158,6 +158,7 @@ SIGNATURES = {
     "dgmr_exceedance_table": [P, L, P, i, L, i, i, P, i, P, P],
     "dgmr_block_match": [P, P, L, L, i, i, i, i, i, f, i, P, P, P, P],
     "dgmr_advect": [P, L, P, L, L, i, i, i, i, f, f, i, P, L, L, P],
+    "dgmr_lk_refine": [P, P, L, L, i, i, i, i, P, P, i, f, P, P, P, P],
     "dgmr_spectral_ar": [P, L, P, L, L, P, i, i, i, i, i, i, P, L, L, P],
     "dgmr_spectral_ar2": [P, L, P, L, P, L, L, P, L, i, i, i, i, i, i, P, L, L, P],
     "dgmr_advect_series": [P, L, L, P, L, i, L, i, i, i, i, f, f, i, P, L, L, P],

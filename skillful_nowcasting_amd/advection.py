@@ -3,8 +3,10 @@ paper plots DGMR against; INTEGRATION.md "A baseline to beat").
 
   * `block_match`: per block of `next`, the integer displacement (dy, dx) of least squared difference against `prev` - the echo
     moved by +d between the two frames - with the costs of its four neighbours and the block's wet count;
-  * `motion_field`: block matching over consecutive context frames, a parabola through the neighbour costs for the sub-pixel part,
-    the pairs averaged, the lattice smoothed and filled;
+  * `lk_refine`: per block, a few Gauss-Newton steps on the squared difference from the integer match (Lucas-Kanade on the block
+    lattice, `dgmr_lk_refine`) with the structure tensor's eigenvalues, which say whether the block shows its motion at all;
+  * `motion_field`: block matching over consecutive context frames, a parabola through the neighbour costs for the sub-pixel part
+    (or, `subpixel="lk"`, the refinement above), the pairs averaged, the lattice smoothed and filled;
   * `advect`: the last frame extrapolated along the field for all lead times, each lead time interpolating the source once;
   * `advect_series`: the same with a source of its own per lead time and one field per group of planes (`dgmr_advect_series`) -
     what `stochastic.EnsembleAdvectionNowcaster` moves its members with;
@@ -31,7 +33,11 @@ MAX_RADIUS = 16
 MAX_STEPS = 64
 CONTEXT_FRAMES = 4  # at most this many of the latest frames give the motion
 
+LK_MAX_ITERATIONS = 16
+SUBPIXEL = ("parabola", "lk")
+
 BlockMatch = namedtuple("BlockMatch", ["disp", "cost", "wet"])
+LkRefine = namedtuple("LkRefine", ["v", "eig", "residual"])
 
 
 def _check_match(h: int, w: int, block: int, stride: int, radius: int, min_wet: int):
@@ -193,6 +199,92 @@ def advect_reference(x, field, steps: int, origin: float = 0.0, spacing: float =
     return out
 
 
+def _check_lk(iterations, eig_ratio):
+    """-> (iterations, eig_ratio rounded to fp32, as the kernel takes it)"""
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= LK_MAX_ITERATIONS:
+        raise ValueError(f"iterations={iterations!r} must be an integer 1 ... {LK_MAX_ITERATIONS}")
+    ratio = float(np.float32(eig_ratio))
+    if not (ratio >= 0 and np.isfinite(ratio)):
+        raise ValueError(f"eig_ratio={eig_ratio} must be finite and not negative")
+    return int(iterations), ratio
+
+
+def lk_conditioned(eig, eig_ratio: float = 0.01):
+    """bool [...]: the blocks of eig [..., 2] = (lambda_min, lambda_max) whose motion `lk_refine` solves for: lambda_min > 0 and
+    lambda_min >= eig_ratio lambda_max (eig_ratio rounded to fp32).  numpy arrays and torch tensors alike."""
+    ratio = _check_lk(1, eig_ratio)[1]
+    return (eig[..., 0] > 0) & (eig[..., 0] >= ratio * eig[..., 1])
+
+
+def lk_refine_reference(prev, nxt, disp, cost, block: int = 32, stride: int = 16, iterations: int = 4,
+                        eig_ratio: float = 0.01) -> LkRefine:
+    """The specification of `dgmr_lk_refine`, in float64 numpy: the integer block match refined to sub-pixel motion by Gauss-Newton
+    steps on the block's squared difference (Lucas-Kanade, forward-additive, with the template's gradient).
+
+    prev, nxt: fp32 [N, H, W], missing elements read as 0; disp [N, By, Bx, 2], cost [N, By, Bx, 5]: `block_match_reference`'s.  Per
+    plane and block with corner (y0, x0) = (by stride, bx stride) and integer match d0 = disp, over the interior I of the `nxt` block,
+    (y0 + i, x0 + j) with 1 <= i, j <= block - 2, Q = nxt:
+
+      g = (gy, gx)        central differences of Q, 0.5 (Q[y + 1][x] - Q[y - 1][x]) and the same along x: all taps inside the block
+      G = sum_I g g^T;    eig = (lambda_min, lambda_max) = (tr -+ sqrt(max(tr^2 - 4 det, 0))) / 2
+      conditioned:        lambda_min > 0 and lambda_min >= eig_ratio lambda_max (`lk_conditioned`; eig_ratio rounded to fp32)
+      d = d0; `iterations` times, for a conditioned block:
+          r(p) = Q(p) - s(p - d), s the bilinear interpolation of prev with zero taps outside the frame (`advect_reference`'s);
+          b = -sum_I g r;  delta = G^-1 b;  d <- clip(d + delta, d0 - 1, d0 + 1) per axis
+      v[N, By, Bx, 2]     float64  d; d0 for a block that is not conditioned
+      eig[N, By, Bx, 2]   float64
+      residual[N, By, Bx] float64  sum_I r^2 at the final d
+    A dry block (cost[..., 0] not finite) gets v = (0, 0), eig = (0, 0), residual = +inf.  G is formed once, and the start is the block
+    match, so there is no pyramid: motion beyond block matching's radius stays out of reach."""
+    q = np.asarray(nxt, dtype=np.float32)
+    p = np.asarray(prev, dtype=np.float32)
+    if q.ndim != 3 or p.shape != q.shape:
+        raise ValueError(f"prev and nxt must be [N, H, W] of one shape, got {p.shape} and {q.shape}")
+    n, h, w = q.shape
+    by, bx = _check_match(h, w, block, stride, 1, 0)
+    iterations, ratio = _check_lk(iterations, eig_ratio)
+    disp, cost = np.asarray(disp), np.asarray(cost)
+    if disp.shape != (n, by, bx, 2) or cost.shape != (n, by, bx, 5):
+        raise ValueError(f"disp and cost must be [{n}, {by}, {bx}, 2] and [{n}, {by}, {bx}, 5], got {disp.shape} and {cost.shape}")
+    with np.errstate(invalid="ignore"):
+        p = np.where(p >= 0, p, np.float32(0)).astype(np.float64)
+        q = np.where(q >= 0, q, np.float32(0)).astype(np.float64)
+    inner = np.arange(1, block - 1)
+    yy = (np.arange(by) * stride)[:, None, None, None] + inner[None, None, :, None]  # [By, 1, m, 1]
+    xx = (np.arange(bx) * stride)[None, :, None, None] + inner[None, None, None, :]  # [1, Bx, 1, m]
+    v = np.zeros((n, by, bx, 2))
+    eig = np.zeros((n, by, bx, 2))
+    residual = np.full((n, by, bx), np.inf)
+    for i in range(n):
+        blocks = np.lib.stride_tricks.sliding_window_view(q[i], (block, block))[::stride, ::stride]  # [By, Bx, block, block]
+        big_q = blocks[..., 1:-1, 1:-1]
+        gy = 0.5 * (blocks[..., 2:, 1:-1] - blocks[..., :-2, 1:-1])
+        gx = 0.5 * (blocks[..., 1:-1, 2:] - blocks[..., 1:-1, :-2])
+        gyy, gxy, gxx = (gy * gy).sum(axis=(-1, -2)), (gy * gx).sum(axis=(-1, -2)), (gx * gx).sum(axis=(-1, -2))
+        tr, det = gyy + gxx, gyy * gxx - gxy * gxy
+        root = np.sqrt(np.maximum(tr * tr - 4.0 * det, 0.0))
+        e = np.stack([0.5 * (tr - root), 0.5 * (tr + root)], axis=-1)
+        wet = np.isfinite(cost[i, ..., 0])
+        cond = wet & lk_conditioned(e, ratio)
+        det = np.where(cond, det, 1.0)
+        d0 = disp[i].astype(np.float64)
+        d = d0.copy()
+
+        def differences(d):
+            return big_q - _sample(p[i], yy - d[..., 0, None, None], xx - d[..., 1, None, None])
+
+        for _ in range(iterations):
+            r = differences(d)
+            b_y, b_x = -(gy * r).sum(axis=(-1, -2)), -(gx * r).sum(axis=(-1, -2))
+            delta = np.stack([(gxx * b_y - gxy * b_x) / det, (gyy * b_x - gxy * b_y) / det], axis=-1)
+            d = np.where(cond[..., None], np.clip(d + delta, d0 - 1.0, d0 + 1.0), d0)
+        r = differences(d)
+        v[i] = np.where(wet[..., None], d, 0.0)
+        eig[i] = np.where(wet[..., None], e, 0.0)
+        residual[i] = np.where(wet, (r * r).sum(axis=(-1, -2)), np.inf)
+    return LkRefine(v, eig, residual)
+
+
 # ---- the device path -------------------------------------------------------------------------------------------------------------
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -237,6 +329,43 @@ def block_match(prev: torch.Tensor, nxt: torch.Tensor, block: int = 32, stride: 
         call("dgmr_block_match", prev.data_ptr(), nxt.data_ptr(), ps, n, h, w, block, stride, radius, float(wet_threshold), min_wet,
              disp.data_ptr(), cost.data_ptr(), wet.data_ptr(), _stream(device))
     return BlockMatch(disp, cost, wet)
+
+
+def lk_refine(prev: torch.Tensor, nxt: torch.Tensor, match: BlockMatch, block: int = 32, stride: int = 16, iterations: int = 4,
+              eig_ratio: float = 0.01) -> LkRefine:
+    """`lk_refine_reference` for torch tensors, results on the inputs' device: v fp32 [N, By, Bx, 2], eig float64 [N, By, Bx, 2],
+    residual float64 [N, By, Bx].  prev, nxt: `block_match`'s layouts and rules; match: its result for the same frames, block and
+    stride.  On a HIP device one `dgmr_lk_refine` on the current stream, nothing synchronised; on the CPU the float64 reference,
+    v rounded to fp32."""
+    if prev.shape != nxt.shape or prev.device != nxt.device:
+        raise ValueError(f"prev {tuple(prev.shape)} on {prev.device} and nxt {tuple(nxt.shape)} on {nxt.device} must match")
+    prev, ps = _planes(prev, "prev")
+    nxt, ns = _planes(nxt, "nxt")
+    n, h, w = (int(v) for v in prev.shape)
+    by, bx = _check_match(h, w, block, stride, 1, 0)
+    iterations, ratio = _check_lk(iterations, eig_ratio)
+    disp, cost = match.disp, match.cost
+    if (tuple(disp.shape) != (n, by, bx, 2) or disp.dtype != torch.int32 or tuple(cost.shape) != (n, by, bx, 5) or
+            cost.dtype != torch.float32 or disp.device != prev.device or cost.device != prev.device):
+        raise ValueError(f"match must hold block_match's int32 [{n}, {by}, {bx}, 2] disp and float32 [{n}, {by}, {bx}, 5] cost on "
+                         f"{prev.device}, got {disp.dtype} {tuple(disp.shape)} and {cost.dtype} {tuple(cost.shape)}")
+    if not prev.is_cuda:
+        ref = lk_refine_reference(prev.numpy(), nxt.numpy(), disp.numpy(), cost.numpy(), block, stride, iterations, ratio)
+        return LkRefine(torch.from_numpy(ref.v.astype(np.float32)), torch.from_numpy(ref.eig), torch.from_numpy(ref.residual))
+    from ._lib import call
+
+    if ps != ns:
+        prev, nxt = prev.contiguous(), nxt.contiguous()
+        ps = h * w
+    disp, cost = disp.contiguous(), cost.contiguous()
+    device = prev.device
+    with torch.cuda.device(device):
+        v = torch.empty((n, by, bx, 2), dtype=torch.float32, device=device)
+        eig = torch.empty((n, by, bx, 2), dtype=torch.float64, device=device)
+        residual = torch.empty((n, by, bx), dtype=torch.float64, device=device)
+        call("dgmr_lk_refine", prev.data_ptr(), nxt.data_ptr(), ps, n, h, w, block, stride, disp.data_ptr(), cost.data_ptr(), iterations,
+             ratio, v.data_ptr(), eig.data_ptr(), residual.data_ptr(), _stream(device))
+    return LkRefine(v, eig, residual)
 
 
 def advect(x: torch.Tensor, field: torch.Tensor, steps: int, origin: float = 0.0, spacing: float = 1.0,
@@ -489,7 +618,8 @@ def _subpixel(c0, cm, cp):
 
 
 def motion_field(frames: torch.Tensor, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
-                 min_wet: Optional[int] = None, smooth: int = 2) -> torch.Tensor:
+                 min_wet: Optional[int] = None, smooth: int = 2, subpixel: str = "parabola", lk_iterations: int = 4,
+                 eig_ratio: float = 0.01) -> torch.Tensor:
     """Motion in pixels per frame on the block lattice: fp32 [N, By, Bx, 2] = (vy, vx); node (by, bx) stands for the block's centre,
     pixel ((block - 1) / 2 + by stride, (block - 1) / 2 + bx stride) - `advect`'s origin and spacing (`lattice_geometry`).
 
@@ -498,11 +628,18 @@ def motion_field(frames: torch.Tensor, block: int = 32, stride: int = 16, radius
     vector is the integer displacement plus, per axis, clip(0.5 (c- - c+) / (c- - 2 c0 + c+), +-0.5) where that denominator is
     positive (else 0).  The pairs are averaged, weighted by usability; then a normalised box smoothing over (2 smooth + 1)^2 nodes,
     sum w v / sum w with w = 1 at nodes that had a usable pair; nodes with no usable neighbour take the plane's mean usable vector,
-    (0, 0) if there is none.  All of this after `block_match` is torch in float64 on the lattice, on the frames' device."""
+    (0, 0) if there is none.  All of this after `block_match` is torch in float64 on the lattice, on the frames' device.
+
+    subpixel="lk" (the parabola is biased towards the integer by up to a third of a pixel; the lead time multiplies that): one
+    `lk_refine` with lk_iterations and eig_ratio over the same pairs after the `block_match`; a block is usable when it is usable
+    above AND conditioned (`lk_conditioned`: a block of stripes says nothing about the motion along them, and block matching's
+    exact 0 there is no measurement), and its vector is the refinement's v.  Averaging, smoothing and fill are the same."""
     if frames.dim() != 4 or frames.shape[0] < 2 or frames.dtype != torch.float32:
         raise ValueError(f"frames must be a float32 [T_in >= 2, N, H, W] tensor, got {frames.dtype} {tuple(frames.shape)}")
     if smooth < 0:
         raise ValueError(f"smooth={smooth} must not be negative")
+    if subpixel not in SUBPIXEL:
+        raise ValueError(f"subpixel={subpixel!r}, {SUBPIXEL} are supported")
     frames = frames.contiguous()
     pairs, n, h, w = frames.shape[0] - 1, *(int(v) for v in frames.shape[1:])
     res = block_match(frames[:-1].reshape(pairs * n, h, w), frames[1:].reshape(pairs * n, h, w), block, stride, radius, wet_threshold,
@@ -511,8 +648,14 @@ def motion_field(frames: torch.Tensor, block: int = 32, stride: int = 16, radius
     cost = res.cost.view(pairs, n, by, bx, 5).to(torch.float64)
     disp = res.disp.view(pairs, n, by, bx, 2).to(torch.float64)
     usable = torch.isfinite(cost).all(dim=-1)
-    c = torch.where(usable[..., None], cost, torch.zeros_like(cost))
-    v = disp + torch.stack([_subpixel(c[..., 0], c[..., 1], c[..., 2]), _subpixel(c[..., 0], c[..., 3], c[..., 4])], dim=-1)
+    if subpixel == "lk":
+        lk = lk_refine(frames[:-1].reshape(pairs * n, h, w), frames[1:].reshape(pairs * n, h, w), res, block, stride, lk_iterations,
+                       eig_ratio)
+        usable = usable & lk_conditioned(lk.eig, eig_ratio).view(pairs, n, by, bx)
+        v = lk.v.view(pairs, n, by, bx, 2).to(torch.float64)
+    else:
+        c = torch.where(usable[..., None], cost, torch.zeros_like(cost))
+        v = disp + torch.stack([_subpixel(c[..., 0], c[..., 1], c[..., 2]), _subpixel(c[..., 0], c[..., 3], c[..., 4])], dim=-1)
     u = usable.to(torch.float64)
     count = u.sum(dim=0)                                   # [N, By, Bx]
     have = count > 0
@@ -546,15 +689,30 @@ def persistence_nowcast(last: torch.Tensor, forecast_steps: int) -> torch.Tensor
 class AdvectionNowcaster:
     """Lagrangian persistence: the motion of the last (at most 4) context frames by `motion_field`, the last frame extrapolated along
     it by `advect` for `forecast_steps` lead times.  One member: no growth or decay, no perturbation.  `last_field`: the motion field
-    of the latest call, [planes, By, Bx, 2] in pixels per frame, planes in (B, C) order."""
+    of the latest call, [planes, By, Bx, 2] in pixels per frame, planes in (B, C) order.  subpixel, lk_iterations, eig_ratio
+    (keyword-only, or `refine_motion` later): `motion_field`'s; the default "parabola" is the field of before, "lk" the Lucas-Kanade
+    refinement."""
 
     def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
-                 min_wet: Optional[int] = None, smooth: int = 2):
+                 min_wet: Optional[int] = None, smooth: int = 2, *, subpixel: str = "parabola", lk_iterations: int = 4,
+                 eig_ratio: float = 0.01):
         if not 1 <= int(forecast_steps) <= MAX_STEPS:
             raise ValueError(f"forecast_steps={forecast_steps}, 1 ... {MAX_STEPS} are supported")
         self.forecast_steps = int(forecast_steps)
         self.params = dict(block=block, stride=stride, radius=radius, wet_threshold=wet_threshold, min_wet=min_wet, smooth=smooth)
+        self.refine_motion(subpixel, lk_iterations, eig_ratio)
         self.last_field = None
+
+    def refine_motion(self, subpixel: str = "lk", lk_iterations: int = 4, eig_ratio: float = 0.01):
+        """Choose `motion_field`'s sub-pixel method -> self, for `EnsembleAdvectionNowcaster(...).refine_motion()`: "lk" (the
+        Lucas-Kanade refinement, with lk_iterations and eig_ratio) or "parabola" (the field of before).  Kept in `params`, which
+        every `motion_field` call of the nowcaster takes.  (A method beside the constructor's keywords: a subclass whose positional
+        order is fixed has no room for them.)"""
+        if subpixel not in SUBPIXEL:
+            raise ValueError(f"subpixel={subpixel!r}, {SUBPIXEL} are supported")
+        _check_lk(lk_iterations, eig_ratio)
+        self.params.update(subpixel=subpixel, lk_iterations=int(lk_iterations), eig_ratio=float(eig_ratio))
+        return self
 
     def _run(self, context: torch.Tensor, out: torch.Tensor, planes_per_case: int) -> None:
         """context [T_in, B * C, H, W]; out [B, T, C, H, W]"""

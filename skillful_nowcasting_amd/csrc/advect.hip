@@ -40,6 +40,23 @@
 //   D = D + v';  out[n, t][p] = s_t(p - D)
 // An axis of v' takes both components of the direction: 2 x 6 rounded operations for their interpolations and 2 for the fmas, 14 on
 // top of the 10 per step - (10 + 14) per step + 1, on two axes - c' = 50.  a = 0 returns v itself (fmaf(0, u, v) = v for finite u).
+//
+// Lucas-Kanade refinement (dgmr_lk_refine).  One workgroup of 256 threads per (plane, block), block matching's grid.  Thread 0 reads
+// the block's minimum cost and displacement d0; a dry block writes its outputs and leaves before anything is staged.  Otherwise
+// the `next` block (B x B) and the (B + 2)^2 window of `prev` whose corner is (y0 - d0y - 1, x0 - d0x - 1) are staged in LDS
+// (8.7 KiB at B = 32; elements outside the frame and missing ones as 0).  d stays within d0 +- 1, so the sample of interior pixel
+// (i, j) sits at window coordinate (i + 1 - ey, j + 1 - ex) with e = d - d0 in [-1, 1]: between i and i + 2, its four taps between
+// i and i + 3 <= B + 1 - no tap leaves the window, and the position is formed from numbers below 64, not from frame coordinates.
+// A thread owns the interior pixels e = tid + 256 k in row-major order (900 at B = 32: k < 4; 196 at B = 16: k < 1) and keeps their
+// Q, gy, gx in registers through the iterations.  The sums (G once, b per iteration, the residual at the end): fp32 fmaf per thread
+// in k order, then float64 - xor butterflies over the wave's 64 lanes (every lane ends with the same bits: a + b = b + a), the four
+// waves' sums through LDS, added in wave order by every thread, which then solves the 2 x 2 system in float64 for itself from
+// identical values; control flow stays uniform.  No atomics: two launches give the same bits.  The LDS slots of successive sums
+// alternate between two sets, so one barrier per sum is enough.
+// Window pitch B + 2 words.  The lanes of a 32-lane group read B - 2 consecutive words of one window row and continue in the next:
+// at B = 32 that is 30 + 2 lanes, the two stragglers a pitch (34 = 2 mod 32) further, on banks two of the 30 hold - a two-way
+// conflict on two banks, one extra LDS cycle per tap read.  Only a pitch of 30 or 62 (mod 32: the rows of a group tiling the banks)
+// is free of it; 62 would nearly double the window for a cycle per read in a kernel that block matching outweighs many times over.
 #include "common.h"
 
 namespace {
@@ -277,7 +294,215 @@ __global__ __launch_bounds__(256) void advect_kernel(AdvGeom g) {
     }
 }
 
+// ---- Lucas-Kanade refinement of the block match ---------------------------------------------------------------------------------
+constexpr int LK_THREADS = 256, LK_WAVES = LK_THREADS / 64, LK_MAX_ITERATIONS = 16;
+
+struct LkGeom {
+    const float* prev;
+    const float* next;
+    const int32_t* disp;
+    const float* cost;
+    int64_t plane_stride;
+    int H, W, stride, By, Bx, iterations;
+    float eig_ratio;
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // both lanes of a pair form a + b: every lane ends with the same bits
+    return v;
+}
+
+// The workgroup's sums of NV per-thread values, in every thread: lanes by butterflies, the waves' sums from LDS in wave order.
+// `slot` alternates between the two sets of LDS words, so a set is rewritten only after a barrier that follows its last read.
+template <int NV>
+__device__ __forceinline__ void lk_sums(const float (&part)[NV], double (*s_red)[LK_WAVES][3], int& slot, int tid, double (&total)[NV]) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const double s = wave_sum_f64((double)part[q]);
+        if ((tid & 63) == 0) s_red[slot][tid >> 6][q] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; ++q) total[q] = ((s_red[slot][0][q] + s_red[slot][1][q]) + s_red[slot][2][q]) + s_red[slot][3][q];
+    slot ^= 1;
+}
+
+// prev at window coordinate (fi - ey, fj - ex): source_sample's order of operations on the staged window.  fi, fj in [2, B - 1] and
+// ey, ex in [-1, 1] keep the four taps inside rows and columns 1 ... B + 1 of the B + 2; the clamp maps a NaN to 0, also inside.
+template <int B>
+__device__ __forceinline__ float lk_sample(const float* s_win, float fi, float fj, float ey, float ex) {
+    constexpr int WP = B + 2;
+    const float sy = fminf(fmaxf(fi - ey, 0.f), (float)B), sx = fminf(fmaxf(fj - ex, 0.f), (float)B);
+    const float fy0 = floorf(sy), fx0 = floorf(sx);
+    const float fy = sy - fy0, fx = sx - fx0;
+    const float* w = s_win + (int)fy0 * WP + (int)fx0;
+    const float top = lerp_fma(w[0], w[1], fx);
+    const float bot = lerp_fma(w[WP], w[WP + 1], fx);
+    return lerp_fma(top, bot, fy);
+}
+
+// eig = (lambda_min, lambda_max) of G = [[gyy, gxy], [gxy, gxx]] and its determinant, float64 and uncontracted: the expressions of
+// the specification, operation for operation
+__device__ __forceinline__ void lk_eigen(double gyy, double gxy, double gxx, double& lmin, double& lmax, double& det) {
+#pragma clang fp contract(off)
+    const double tr = gyy + gxx;
+    const double a = gyy * gxx, b = gxy * gxy;
+    det = a - b;
+    const double t2 = tr * tr, d4 = 4.0 * det;
+    const double root = sqrt(fmax(t2 - d4, 0.0));
+    lmin = 0.5 * (tr - root);
+    lmax = 0.5 * (tr + root);
+}
+
+// delta = G^-1 b with b = -(sy, sx), the sums of g r
+__device__ __forceinline__ void lk_solve(double gyy, double gxy, double gxx, double det, double sy, double sx, double& dy, double& dx) {
+#pragma clang fp contract(off)
+    const double by = -sy, bx = -sx;
+    const double p0 = gxx * by, p1 = gxy * bx, p2 = gyy * bx, p3 = gxy * by;
+    dy = (p0 - p1) / det;
+    dx = (p2 - p3) / det;
+}
+
+template <int B>
+__global__ __launch_bounds__(LK_THREADS) void lk_refine_kernel(LkGeom g, float* __restrict__ v, double* __restrict__ eig,
+                                                               double* __restrict__ residual) {
+    constexpr int M = B - 2, NI = M * M, K = (NI + LK_THREADS - 1) / LK_THREADS, WP = B + 2;
+    __shared__ float s_next[B * B];
+    __shared__ float s_win[WP * WP];
+    __shared__ double s_red[2][LK_WAVES][3];
+    __shared__ int s_head[3];  // not dry, d0y, d0x
+    const int tid = threadIdx.x;
+    const int per_plane = g.By * g.Bx;
+    const int64_t id = blockIdx.x;
+    const int64_t n = id / per_plane;
+    const int b = (int)(id - n * per_plane);
+    const int by = b / g.Bx, bx = b - by * g.Bx;
+    const int y0 = by * g.stride, x0 = bx * g.stride;  // y0 + B <= H, x0 + B <= W
+    if (tid == 0) {
+        const float c0 = g.cost[id * 5];
+        s_head[0] = c0 - c0 == 0.f ? 1 : 0;  // finite
+        s_head[1] = g.disp[id * 2];
+        s_head[2] = g.disp[id * 2 + 1];
+    }
+    __syncthreads();
+    if (!s_head[0]) {  // dry (uniform over the workgroup): nothing is staged
+        if (tid == 0) {
+            v[id * 2] = 0.f;
+            v[id * 2 + 1] = 0.f;
+            eig[id * 2] = 0.0;
+            eig[id * 2 + 1] = 0.0;
+            residual[id] = (double)__builtin_inff();
+        }
+        return;
+    }
+    const int d0y = s_head[1], d0x = s_head[2];
+    const float* nx = g.next + n * g.plane_stride + (int64_t)y0 * g.W + x0;
+    for (int e = tid; e < B * B; e += LK_THREADS) {
+        const int i = e / B, j = e - i * B;
+        s_next[e] = present_or_zero(nx[(int64_t)i * g.W + j]);
+    }
+    const float* pv = g.prev + n * g.plane_stride;
+    const int64_t wy0 = (int64_t)y0 - d0y - 1, wx0 = (int64_t)x0 - d0x - 1;  // 64-bit: any disp, whatever wrote it, only fails the test below
+    for (int e = tid; e < WP * WP; e += LK_THREADS) {
+        const int i = e / WP, j = e - i * WP;
+        const int64_t y = wy0 + i, x = wx0 + j;
+        s_win[e] = (y >= 0 && y < g.H && x >= 0 && x < g.W) ? present_or_zero(pv[y * g.W + x]) : 0.f;
+    }
+    __syncthreads();
+    float q[K], gy[K], gx[K], fi[K], fj[K];
+    float part3[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int e = tid + k * LK_THREADS;
+        q[k] = gy[k] = gx[k] = 0.f;
+        fi[k] = fj[k] = 2.f;
+        if (e < NI) {
+            const int i = 1 + e / M, j = 1 + (e - (e / M) * M);
+            const float* c = s_next + i * B + j;
+            q[k] = c[0];
+            gy[k] = 0.5f * (c[B] - c[-B]);
+            gx[k] = 0.5f * (c[1] - c[-1]);
+            fi[k] = (float)(i + 1);
+            fj[k] = (float)(j + 1);
+            part3[0] = fmaf(gy[k], gy[k], part3[0]);
+            part3[1] = fmaf(gy[k], gx[k], part3[1]);
+            part3[2] = fmaf(gx[k], gx[k], part3[2]);
+        }
+    }
+    int slot = 0;
+    double G[3];
+    lk_sums<3>(part3, s_red, slot, tid, G);
+    double lmin, lmax, det;
+    lk_eigen(G[0], G[1], G[2], lmin, lmax, det);
+    const bool conditioned = lmin > 0.0 && lmin >= (double)g.eig_ratio * lmax;  // the same bits in every thread
+    const float fy0 = (float)d0y, fx0 = (float)d0x;
+    float dy = fy0, dx = fx0;
+    if (conditioned) {
+        for (int it = 0; it < g.iterations; ++it) {
+            const float ey = dy - fy0, ex = dx - fx0;  // in [-1, 1]
+            float part2[2] = {0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                if (tid + k * LK_THREADS < NI) {
+                    const float r = q[k] - lk_sample<B>(s_win, fi[k], fj[k], ey, ex);
+                    part2[0] = fmaf(gy[k], r, part2[0]);
+                    part2[1] = fmaf(gx[k], r, part2[1]);
+                }
+            }
+            double s[2], ddy, ddx;
+            lk_sums<2>(part2, s_red, slot, tid, s);
+            lk_solve(G[0], G[1], G[2], det, s[0], s[1], ddy, ddx);
+            dy = fminf(fmaxf((float)((double)dy + ddy), fy0 - 1.f), fy0 + 1.f);
+            dx = fminf(fmaxf((float)((double)dx + ddx), fx0 - 1.f), fx0 + 1.f);
+        }
+    }
+    const float ey = dy - fy0, ex = dx - fx0;
+    float part1[1] = {0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (tid + k * LK_THREADS < NI) {
+            const float r = q[k] - lk_sample<B>(s_win, fi[k], fj[k], ey, ex);
+            part1[0] = fmaf(r, r, part1[0]);
+        }
+    }
+    double res[1];
+    lk_sums<1>(part1, s_red, slot, tid, res);
+    if (tid == 0) {
+        v[id * 2] = dy;
+        v[id * 2 + 1] = dx;
+        eig[id * 2] = lmin;
+        eig[id * 2 + 1] = lmax;
+        residual[id] = res[0];
+    }
+}
+
 }  // namespace
+
+extern "C" int dgmr_lk_refine(const float* prev, const float* next, int64_t plane_stride, int64_t N, int H, int W, int block, int stride,
+                              const int32_t* disp, const float* cost, int iterations, float eig_ratio, float* v, double* eig,
+                              double* residual, void* stream) {
+    const char* fn = "dgmr_lk_refine";
+    DGMR_CHECK_ARG(prev && next && disp && cost && v && eig && residual, "%s: null pointer", fn);
+    DGMR_CHECK_ARG(block == 16 || block == 32, "%s: block=%d, 16 and 32 are supported", fn, block);
+    DGMR_CHECK_ARG(stride >= 1 && stride <= block, "%s: stride=%d must be 1 ... block=%d", fn, stride, block);
+    DGMR_CHECK_ARG(iterations >= 1 && iterations <= LK_MAX_ITERATIONS, "%s: iterations=%d must be 1 ... %d", fn, iterations, LK_MAX_ITERATIONS);
+    DGMR_CHECK_ARG(eig_ratio >= 0.f && eig_ratio <= 3.0e38f, "%s: eig_ratio=%g must be finite and not negative", fn, (double)eig_ratio);
+    DGMR_CHECK_ARG(N >= 1 && N <= (1 << 24), "%s: N=%lld planes out of range", fn, (long long)N);
+    DGMR_CHECK_ARG(H >= block && W >= block, "%s: H=%d and W=%d must be at least block=%d", fn, H, W, block);
+    DGMR_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: a plane of %d x %d elements is out of range", fn, H, W);
+    DGMR_CHECK_ARG(plane_stride >= 0 && plane_stride <= INT64_MAX / 4 / N, "%s: plane_stride=%lld out of range", fn, (long long)plane_stride);
+    const int By = (H - block) / stride + 1, Bx = (W - block) / stride + 1;
+    DGMR_CHECK_ARG(N * By * Bx <= (1ll << 30), "%s: %lld blocks are out of range", fn, (long long)(N * By * Bx));
+    const LkGeom g{prev, next, disp, cost, plane_stride, H, W, stride, By, Bx, iterations, eig_ratio};
+    const dim3 grid((unsigned)(N * By * Bx)), threads(LK_THREADS);
+    if (block == 16)
+        hipLaunchKernelGGL(lk_refine_kernel<16>, grid, threads, 0, ST, g, v, eig, residual);
+    else
+        hipLaunchKernelGGL(lk_refine_kernel<32>, grid, threads, 0, ST, g, v, eig, residual);
+    DGMR_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int dgmr_block_match(const float* prev, const float* next, int64_t plane_stride, int64_t N, int H, int W, int block, int stride,
                                 int radius, float wet_threshold, int min_wet, int32_t* disp, float* cost, int32_t* wet, void* stream) {

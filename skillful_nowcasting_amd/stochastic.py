@@ -755,7 +755,9 @@ class EnsembleAdvectionNowcaster(AdvectionNowcaster):
     a plane draws one pair (eps_par, eps_perp) of unit Gaussians, its velocity at lead time t is v + eps_par sigma_par[t] u +
     eps_perp sigma_perp[t] u_perp with u = `unit_directions(last_field)` and sigma = `velocity_scale` (fp32 [T, 2],
     `velocity_perturbation_scale`), and one `advect_series_perturbed` moves all members.  The pairs of the latest call are
-    `last_velocity_noise` (fp32 [planes, M, 2])."""
+    `last_velocity_noise` (fp32 [planes, M, 2]).
+    `refine_motion("lk")` (`AdvectionNowcaster`'s; a method for `perturb_velocities`' reason) switches `motion_field`'s Lucas-Kanade
+    refinement on - for the field that moves the members and that aligns the context frames for rho="estimate"."""
 
     def __init__(self, forecast_steps: int = 18, block: int = 32, stride: int = 16, radius: int = 8, wet_threshold: float = 0.1,
                  min_wet: Optional[int] = None, smooth: int = 2, window: int = 128, threshold: float = 0.1, pad: float = 5.0,
