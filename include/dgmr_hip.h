@@ -665,6 +665,27 @@ int dgmr_exceedance_table(const float* forecast, int64_t member_stride, const fl
                           const float* thresholds, int K, int64_t* table, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fractions skill score sums (fss.py: fss_sums, FractionsVerifier; csrc/fss.hip).  New symbol, same ABI version.
+ * forecast, member_stride, observed, M, N, H, W, thresholds, K: as in dgmr_exceedance_table, with the same missing rule (an observed
+ * element is missing when !(y >= 0); at a missing pixel neither the observation nor any member is an event; NaN reaches no threshold),
+ * fp32 comparisons, alignment rules and refusals, but 1 <= K <= 8.  radii: S host integers, 1 <= S <= 8, distinct, 0 <= r <= 32, in
+ * any order; the neighbourhood of a pixel is the (2 r + 1)^2 square centred on it, the plane zero-padded outside, and every pixel of
+ * the plane is a window centre.  With I_m = present & (x_m >= thr_k), I_o = present & (y >= thr_k), S_m = box_r(I_m), S_o = box_r(I_o)
+ * and S_f = sum_m S_m (integers; the (2 r + 1)^2 normalisation is never applied):
+ *   sums[n][k][s][4]  int64  sum over the centres of plane n of  S_f^2,  S_o^2,  S_f S_o,  sum_m S_m^2
+ *   events[n][k][2]   int64  sum_m sum_pixels I_m,  sum_pixels I_o
+ * One workgroup per 64 x 64 tile of centres and group of thresholds: the tile and a halo of the largest radius are staged in LDS as
+ * one bit per (threshold, field, pixel) by wave ballots, box sums are popcounts of row windows and a running vertical sum, products and
+ * sums are integers (64-bit accumulators), added to outputs the call clears first with 64-bit integer atomics: exact, independent of
+ * the order, no workspace, two calls give the same bits.  Runs on `stream`, does not synchronise.  Argument errors (null pointers, M
+ * outside 1 ... 32, H or W not a multiple of 16, K or S outside 1 ... 8, a radius outside 0 ... 32 or given twice, misaligned pointers
+ * or stride, M^2 (2 R + 1)^4 H W >= 2^63 with R the largest radius: a conservative bound of every sum) return < 0 and set
+ * dgmr_last_error() before anything is enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+int dgmr_fss_sums(const float* forecast, int64_t member_stride, const float* observed, int M, int64_t N, int H, int W,
+                  const float* thresholds, int K, const int* radii, int S, void* sums, void* events, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The advection baseline (advection.py; csrc/advect.hip).  New symbols, same ABI version.
  *
  * Block matching (TREC) between two frames.  prev, next: N fp32 planes of H x W, plane_stride elements apart; an element with

@@ -156,6 +156,7 @@ SIGNATURES = {
     "dgmr_ensemble_scores": [P, L, P, i, L, i, i, POINTER(c_int), i, P, i, P, L, P, P, P, P, P, P],
     "dgmr_radial_psd": [P, L, L, i, i, i, P, L, P, P, P],
     "dgmr_exceedance_table": [P, L, P, i, L, i, i, P, i, P, P],
+    "dgmr_fss_sums": [P, L, P, i, L, i, i, P, i, POINTER(c_int), i, P, P, P],
     "dgmr_block_match": [P, P, L, L, i, i, i, i, i, f, i, P, P, P, P],
     "dgmr_advect": [P, L, P, L, L, i, i, i, i, f, f, i, P, L, L, P],
     "dgmr_lk_refine": [P, P, L, L, i, i, i, i, P, P, i, f, P, P, P, P],
